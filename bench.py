@@ -6,8 +6,14 @@ HBM:  unproject_heatmaps(softmax aggregation) -> integrate_tensor_3d_with_coordi
 over channels [0:17] of the unprojected volume (the stand-in for V2V)
 -> (N > 1) one all-gather of the (B/N, 17, 3) joints over RCCL.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4] [--no-cpu-baseline]
-                    [--no-secondary] [--dry-run]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-secondary]] [--dry-run]
+
+A plain run does only what the headline figure needs: it builds the frames, settles the
+clock, warms up, times the K steps, writes the last timed step's outputs (--dump-outputs)
+and prints the line.  Everything else described below — telemetry, the measured copy
+bandwidth, the other configs and arithmetic, the CPU baseline, the parity and gather checks —
+runs only with --full.
 
 Process model (the reference's DDP model, /root/reference/train.py:370-382): one process
 per GPU.  Launched by torch.distributed.run (WORLD_SIZE set) every process is one rank.
@@ -24,12 +30,12 @@ needs no GPU (tests/test_bench.py).  --dist-backend gloo --share-device runs the
 step on several ranks sharing cuda:0 with host-side collectives (RCCL refuses two ranks on
 one device): the multi-rank path on a one-GPU box (tests/test_gpu_bench_multirank.py).
 
-Every config also reports `telemetry` (sclk, mclk, socket power, hotspot temperature, GFX
-activity and power-limit residency sampled during an untimed burst of the same step right
-after its timed region) and the line carries `gpu` (UUID, ASIC serial, power cap).
+The line carries `gpu` (UUID, ASIC serial, power cap); with --full every config also reports
+`telemetry` (sclk, mclk, socket power, hotspot temperature, GFX activity and power-limit
+residency sampled during an untimed burst of the same step right after its timed region).
 
-With the default --config 2 the line also carries `secondary` (config 3, bf16, 32 frames,
-with its own roofline block), `config1` (the algebraic path: DLT at batch 1, 4 views x 17
+With --full and the default --config 2 the line also carries `secondary` (config 3, bf16,
+32 frames, with its own roofline block), `config1` (the algebraic path: DLT at batch 1, 4 views x 17
 joints, and the 2D soft-argmax -> DLT chain), `config4` and `config5` (unproject written
 channels-last + the V2V front Conv3d block on bf16 MFMA, 64 frames, MFMA roofline);
 --no-secondary drops them.
@@ -160,16 +166,22 @@ def settle_steps(step, args, clock):
     return n + 8
 
 
-def timed_loop(step, args, clock):
+def timed_loop(step, args, clock, last=None):
+    """Seconds the args.steps timed steps took (max over ranks).  `last`, a list, receives what
+    the last timed step returned; the earlier steps' results are dropped as they return."""
     settle_steps(step, args, clock)
     for _ in range(args.warmup):
         step(False)
     clock.fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step(True)
+    out = step(True)
     clock.fence()
-    return clock.max_over_ranks(time.perf_counter() - t0)
+    elapsed = clock.max_over_ranks(time.perf_counter() - t0)
+    if last is not None:
+        last.append(out)
+    return elapsed
 
 
 # ----------------------------------------------------------------------------- GPU telemetry
@@ -477,19 +489,45 @@ def run_config(name, args, rank, world, device, clock, cuboid=False, cfg=None, f
                   precision=precision)
     wl.starts = starts if starts is not None else [r * cfg["frames"] for r in range(world)]
     wl.reserve_events(args.steps, args.event_stride)
-    elapsed = timed_loop(lambda t: wl.step(t), args, clock)
+    last = []
+    elapsed = timed_loop(lambda t: wl.step(t), args, clock, last)
     E = 2 if cfg["dtype"] == torch.bfloat16 else 4
     frames_total = wl.global_batch * args.steps
     unproj_ms, sa_ms = wl.kernel_ms()
     # every rank samples its own GPU (the line carries the per-rank list at world > 1); the burst
     # runs each rank's local step only — a rank-dependent count of collectives would deadlock
-    tel = telemetry(device, lambda t: wl.step(t, gather=False))
+    tel = telemetry(device, lambda t: wl.step(t, gather=False)) if args.full else None
     launch_bytes = unproject_bytes(cfg, E, cuboid) * cfg["frames"]
-    return dict(cfg=cfg, workload=wl, precision=precision, elapsed=elapsed, fps=frames_total / elapsed,
+    return dict(cfg=cfg, workload=wl, last_outputs=last[0], precision=precision, elapsed=elapsed,
+                fps=frames_total / elapsed,
                 ms_per_step=elapsed / args.steps * 1e3,
                 unproject_ms=unproj_ms, softargmax_ms=sa_ms, launch_bytes=launch_bytes,
                 achieved_gbps=(launch_bytes / (unproj_ms * 1e-3) / 1e9) if unproj_ms else None,
                 path_gbps=frame_bytes(cfg, E, cuboid) * frames_total / elapsed / 1e9, telemetry=tel)
+
+
+DUMP_SAMPLE = 1 << 20     # elements written of an output larger than that (4 MB as float32)
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what the last timed step of the headline workload handed its caller, as
+    float32 <name>.npy files under `path`: the joints it returned (all of them; at N > 1 the
+    gathered joints of every rank) and, of rank 0's unprojected volume and soft-argmax volumes,
+    the same DUMP_SAMPLE seeded element positions on every run.  The frames depend on the
+    arguments alone, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    import torch
+    xyz, sm = res["last_outputs"]
+    vol = res["workload"].last[0]
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("joints", xyz), ("unprojected_volume", vol), ("softargmax_volumes", sm)):
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
+        else:
+            np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def run_config5(args, rank, world, device, clock, cuboid=False):
@@ -876,6 +914,13 @@ def main():
     ap.add_argument("--precision", default="exact", choices=["exact", "fast"],
                     help="the unprojection arithmetic of the headline and its secondary configs (DESIGN.md §4.1a); "
                          "the other arithmetic is reported beside them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's outputs as DIR/<name>.npy (float32; "
+                         "outputs above 2^20 elements as a fixed, seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: telemetry, the measured copy bandwidth, "
+                         "the secondary configs, the other arithmetic, in-kernel coordinates, the CPU baseline and "
+                         "the parity and gather checks (the --no-* options trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--event-stride", type=int, default=4,
                     help="kernel times from HIP events on every K-th timed step (events cost GPU time; "
@@ -931,9 +976,11 @@ def main():
     coll = (f"all_gather joints ({'RCCL' if args.dist_backend == 'nccl' else 'gloo, host tensors'})"
             if world > 1 else None)
     configs = _configs()
-    extras = not args.no_secondary and args.config == "2"
+    extras = args.full and not args.no_secondary and args.config == "2"
 
     main_res = run_config(args.config, args, rank, world, device, clock)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main_res)
     secondary = config1 = in_kernel_coords = cfg4 = cfg5 = sec_res = None
     if extras:
         s = sec_res = run_config("3", args, rank, world, device, clock)
@@ -955,7 +1002,7 @@ def main():
                                         softargmax_ms=o["softargmax_ms"], roofline=roofline(o["cfg"], o, cn, device),
                                         path_algorithmic_gbps=o["path_gbps"],
                                         path_frac=o["path_gbps"] / HBM_PEAK_GBPS, telemetry=o["telemetry"])
-    if not args.no_secondary and not args.no_in_kernel_coords:
+    if args.full and not args.no_secondary and not args.no_in_kernel_coords:
         # the same workload with the coordinate volume formed inside both kernels from the
         # per-frame cuboids instead of read from HBM
         k = run_config(args.config, args, rank, world, device, clock, cuboid=True)
@@ -985,7 +1032,7 @@ def main():
         if rank == 0:
             config1 = run_config1(args, device)
     base = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the CPU leg: the reference algorithm timed on the host, and the timed workloads'
         # outputs checked against the oracle (never inside a timed region)
         base = cpu_baseline()
@@ -1002,7 +1049,7 @@ def main():
     if cfg5 is not None:
         cfg5.pop("parity_inputs", None)
     gather = None
-    if rank == 0 and world > 1:
+    if rank == 0 and world > 1 and args.full:
         gather = verify_gather(main_res)
         if cfg4 is not None:
             cfg4["gather"] = verify_gather(r4)
@@ -1040,7 +1087,7 @@ def main():
                        "views": c["views"], "channels": c["channels"], "heatmap": c["heatmap"],
                        "volume": c["volume"], "joints": c["joints"], "parallelism": f"dp{world}",
                        "collective": coll, **({"device_shared": True} if args.share_device else {})},
-            "roofline": roofline(c, r, args.config, device),
+            "roofline": roofline(c, r, args.config, device if args.full else None),
             "softargmax_ms": r["softargmax_ms"],
             "path_algorithmic_gbps": r["path_gbps"],
             "path_frac": r["path_gbps"] / HBM_PEAK_GBPS,
@@ -1052,6 +1099,7 @@ def main():
             "parity": parity,
             "gather": gather,
             "precision": args.precision,
+            "full": args.full,
             "secondary": secondary,
             "other_precision": other,
             "config1": config1,

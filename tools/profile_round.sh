@@ -10,18 +10,18 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt" -o kt -- \
-    python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-in-kernel-coords > "$out/kt.log" 2>&1
+    python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-in-kernel-coords > "$out/kt.log" 2>&1
 echo "kernel trace done"
 # one config per process: a kernel that serves several configs gets one mean per config
 for cfg in 2 3 4; do
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt_cfg$cfg" -o kt -- \
-      python3 bench.py --config $cfg --steps 20 --warmup 5 --no-secondary --no-cpu-baseline \
+      python3 bench.py --full --config $cfg --steps 20 --warmup 5 --no-secondary --no-cpu-baseline \
       > "$out/kt_cfg$cfg.log" 2>&1
 done
 # the fast arithmetic, configs 2 and 3
 for cfg in 2 3; do
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt_cfg${cfg}_fast" -o kt -- \
-      python3 bench.py --config $cfg --steps 20 --warmup 5 --no-secondary --no-cpu-baseline --precision fast \
+      python3 bench.py --full --config $cfg --steps 20 --warmup 5 --no-secondary --no-cpu-baseline --precision fast \
       > "$out/kt_cfg${cfg}_fast.log" 2>&1
 done
 echo "per-config kernel traces done"
