@@ -64,9 +64,10 @@ extern "C" {
 /* ---- unprojection arithmetic -------------------------------------------- */
 #define MVN_PRECISION_EXACT 0  /* the reference's f32 op order: sum / max / conf* bit-exact,
                                   softmax <= 1e-5 (the default of every other entry point)  */
-#define MVN_PRECISION_FAST  1  /* the north_star contract's tolerance:
-                                  reciprocal projection, max-free view softmax, and for bf16
-                                  maps bf16 bilinear weights on v_dot2 pixel pairs          */
+#define MVN_PRECISION_FAST  1  /* joints within north_star's 1e-4, the volume within the
+                                  project's own bars (below): reciprocal
+                                  projection, max-free view softmax, and for bf16 maps bf16
+                                  bilinear weights on v_dot2 pixel pairs                    */
 
 /* ---- view aggregation (op.py:147-161) ---------------------------------- */
 #define MVN_AGG_SUM      0     /* 'sum'                                           */
@@ -154,9 +155,10 @@ int mvn_unproject_ex(const void* feat, int feat_dtype,
  * mvn_unproject / mvn_unproject_ex / mvn_unproject_cuboid with a selectable arithmetic
  * (op.py:99-163).  Exactly one of coords (B, Vx, Vy, Vz, 3) and cuboids (B, 18; then
  * Vx = Vy = Vz, N <= 8) is non-NULL.  precision = MVN_PRECISION_EXACT is bit-identical
- * to those entry points; MVN_PRECISION_FAST computes the same function within the
- * north_star tolerance (f32 maps: <= 1e-4 max-rel of the volume, measured 2-4e-5; bf16 maps: one bf16 ulp
- * + 2^-8 max|ref|, 2^-7 for softmax; validity masks unchanged), measured in DESIGN.md §4.1a.
+ * to those entry points; MVN_PRECISION_FAST computes the same function with the 3D joints
+ * within north_star's 1e-4 (the only bound north_star sets) and the volume within bars the
+ * project sets itself (f32 maps: <= 1e-4 max-rel of the volume, measured 2-4e-5; bf16 maps: one
+ * bf16 ulp + 2^-8 max|ref|, 2^-7 for softmax; validity masks unchanged), measured in DESIGN.md §4.1a.
  */
 int mvn_unproject_precision(const void* feat, int feat_dtype,
                             const float* proj, const float* coords, const float* cuboids, int transfer_cmu,

@@ -19,8 +19,8 @@ _default_precision = "exact"
 def set_unproject_precision(precision: str) -> str:
     """Process-wide default arithmetic of ``unproject_heatmaps`` calls that pass no
     ``precision=`` (as ``torch.backends`` flags do for matmul): ``'exact'`` (the default: the
-    reference's f32 rounding, 'sum' / 'max' / 'conf*' bit-exact) or ``'fast'`` (the north_star
-    tolerance) — the switch for a model rebound by ``install()``.  Returns the
+    reference's f32 rounding, 'sum' / 'max' / 'conf*' bit-exact) or ``'fast'`` (joints within
+    north_star's 1e-4, the volume within the project's own bars) — the switch for a model rebound by ``install()``.  Returns the
     previous setting."""
     global _default_precision
     precision_code(precision)

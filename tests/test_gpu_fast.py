@@ -1,7 +1,7 @@
 """MVN_PRECISION_FAST unprojection against the pinned C oracle (MI355X only).
 
-The fast mode computes op.py:99-163 within the north_star tolerance instead of the
-reference's rounding: reciprocal projection (one v_rcp per view), the view softmax without
+The fast mode computes op.py:99-163 within the bars below (the joints' is north_star's, the
+volume bars are the project's own) instead of the reference's rounding: reciprocal projection (one v_rcp per view), the view softmax without
 its max pass, and — for bf16 maps — bf16 bilinear weights on bf16 pixel pairs (v_dot2).
 
 Bars (written here):
@@ -120,6 +120,28 @@ def test_fast_falls_back_to_exact_where_it_does_not_apply(device, n_views):
     fast = op.unproject_heatmaps(f, P, c, "softmax", precision="fast")
     exact = op.unproject_heatmaps(f, P, c, "softmax", precision="exact")
     assert torch.equal(fast.view(torch.int32), exact.view(torch.int32))
+
+
+@pytest.mark.parametrize("case", ("eight_views_channels_last", "channels_6", "width_66"))
+def test_fast_falls_back_to_exact_where_the_chunk_kernel_declines(device, case):
+    """The other calls launch_x4 (csrc/unproject_x4.hip) hands to the exact tiled kernel: 8 views
+    written channels-last, 4 views with C % 4 != 0, and maps whose width is no multiple of 4 —
+    precision='fast' returns the exact volume bit for bit."""
+    from mvn_rocm import op, synth, v2v
+    n_views, channels = (8, 8) if case == "eight_views_channels_last" else (4, 6) if case == "channels_6" else (4, 8)
+    vb = synth.volumetric_batch(1, n_views=n_views, channels=channels, heatmap=64, volume=16, seed=48)
+    f, P, c = vb.features.to(device), vb.proj.to(device), vb.coords.to(device)
+    if case == "width_66":
+        g = torch.Generator().manual_seed(48)
+        f = torch.cat([vb.features, torch.randn((1, 4, 8, 64, 2), generator=g)], dim=4).contiguous().to(device)
+        assert f.shape[-1] == 66
+    if case == "eight_views_channels_last":
+        fast, exact = (v2v.unproject_channels_last(f, P, c, "softmax", out_dtype=torch.float32, precision=p)
+                       for p in ("fast", "exact"))
+    else:
+        fast, exact = (op.unproject_heatmaps(f, P, c, "softmax", precision=p) for p in ("fast", "exact"))
+    assert torch.equal(fast.view(torch.int32), exact.view(torch.int32))
+    assert (exact != 0).float().mean() > 0.2 and torch.isfinite(exact).all()
 
 
 # ----------------------------------------------------------------------------- bf16 maps (pixel pairs, v_dot2)
