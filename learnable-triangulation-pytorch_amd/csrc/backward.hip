@@ -57,7 +57,9 @@ __global__ __launch_bounds__(kThreads) void sa_bwd_partials(const TV* __restrict
       const float k = (m == -INFINITY) ? 0.f : __expf(m - x);
       s *= k; t *= k; m = x;
     }
-    const float e = __expf(x - m);
+    // a -inf logit has p = 0 (torch: gradient exactly 0 there) and leaves the running maximum
+    // alone: with m still -inf, x - m would be -inf - -inf = NaN (the forward guards it too)
+    const float e = (x == -INFINITY) ? 0.f : __expf(x - m);
     s += e;
     t = __builtin_fmaf(e, d, t);
   }

@@ -97,6 +97,9 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
     heatmap dtype (float32 for float32 input, as in the reference).  ``precision`` —
     ``'exact'`` or ``'fast'``, default ``set_unproject_precision``'s — selects the arithmetic
     (DESIGN.md §4.1a); the backward is the exact function's in both.
+    The forward takes any number of views; the backward kernels exist for at most 8
+    (csrc/unproject_bwd.hip): ``backward()`` through a call with 9 or more views raises
+    ``_lib.MvnError`` (MVN_ERR_SHAPE) — it never returns a zero gradient.
     """
     agg = aggregation_code(volume_aggregation_method)
     prec = precision_code(precision)

@@ -11,6 +11,8 @@ imports this package.
                          B x J Python loops) — bit-exact with the reference, and the
                          timed CPU baseline on the GPU box
     oracle.restate_np    float64 numpy restatement of the DLT (LAPACK SVD)
+    oracle.backward_cases seeded inputs + float64 autograd references of the backward tests
+                         (tests/test_gpu_backward_shapes.py, tests/test_backward_refs.py)
 
 Pinning: every restatement is checked against tests/golden/*.npz, vectors captured by
 importing the reference itself in the build container (tests/golden/make_golden.py).

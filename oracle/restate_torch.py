@@ -112,6 +112,45 @@ def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_
     return out
 
 
+def triangulate_batch_of_points_f32_design(proj_matricies_batch, points_batch, confidences_batch, grad_out):
+    """Gradients of triangulate_batch_of_points w.r.t. (points, confidences) with the design
+    matrix formed in float32 — the three f32 operations of multiview.py:150-152, as the
+    reference and the HIP kernels form it — and everything after it in float64: A is promoted
+    to a float64 leaf, torch.svd and X[:3] / X[3] run in float64, autograd gives dL/dA, and
+    the chain rule through a_{v,r} = c_v (pt_{v,r} P_v2 - P_vr) is applied in closed form:
+        dL/dpt_{v,r} = c_v (dL/da_{v,r} . P_v2)
+        dL/dc_v      = sum_r dL/da_{v,r} . (pt_{v,r} P_v2 - P_vr)
+    confidences_batch may be None (all ones; grad_conf is then the gradient w.r.t. those ones).
+    Returns (points (B, J, 3), grad_pts (B, N, J, 2), grad_conf (B, N, J)), float64."""
+    P32 = proj_matricies_batch.detach().to(torch.float32)
+    pts32 = points_batch.detach().to(torch.float32)
+    n_batch, n_views, n_joints = pts32.shape[:3]
+    conf32 = (torch.ones(n_batch, n_views, n_joints, dtype=torch.float32) if confidences_batch is None
+              else confidences_batch.detach().to(torch.float32))
+    out = torch.zeros(n_batch, n_joints, 3, dtype=torch.float64)
+    grad_pts = torch.zeros(n_batch, n_views, n_joints, 2, dtype=torch.float64)
+    grad_conf = torch.zeros(n_batch, n_views, n_joints, dtype=torch.float64)
+    for b in range(n_batch):
+        P = P32[b]
+        P64 = P.double()
+        for j in range(n_joints):
+            pts, conf = pts32[b, :, j, :], conf32[b, :, j]
+            A = P[:, 2:3].expand(n_views, 2, 4) * pts.view(n_views, 2, 1)       # multiview.py:150 (f32)
+            A = A - P[:, :2]                                                    # :151
+            A = A * conf.view(-1, 1, 1)                                         # :152
+            A64 = A.double().detach().requires_grad_(True)
+            _, _, V = torch.svd(A64.view(-1, 4))                                # :154, float64
+            X = -V[:, 3]
+            p = X[:3] / X[3]
+            p.backward(grad_out[b, j].double())
+            gA = A64.grad                                                       # (N, 2, 4)
+            out[b, j] = p.detach()
+            grad_pts[b, :, j] = conf.double().view(-1, 1) * (gA * P64[:, 2:3]).sum(-1)
+            row = pts.double().view(n_views, 2, 1) * P64[:, 2:3] - P64[:, :2]   # pt P_2 - P_r
+            grad_conf[b, :, j] = (gA * row).sum((-1, -2))
+    return out, grad_pts, grad_conf
+
+
 def build_coord_volumes(base_points, cuboid_side, volume_size, thetas, kind="coco", transfer_cmu=False,
                         rotate=None):
     """mvn/models/triangulation.py:280-341, the per-frame loop, op for op (torch CPU).

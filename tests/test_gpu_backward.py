@@ -1,7 +1,8 @@
 """Backward kernels vs the reference's autograd (golden gradients) — MI355X only.
 
-Bars: unproject / soft-argmax gradients within 1e-5 max-rel of the reference's f32
-autograd (float atomics reorder the sums; forward samples are bit-exact); DLT gradients
+Bars: unproject and 2D soft-argmax gradients within 1e-5 max-rel of the reference's f32
+autograd (float atomics reorder the sums; forward samples are bit-exact), 3D soft-argmax
+gradients within 1e-4 of it; DLT gradients
 within 1e-5 of a float64 autograd restatement (oracle/restate_torch.py in float64: torch
 svd backward), and within 5e-2 of the f32 reference gradient, whose SVD-backward error is
 itself that large for these 2N x 4 systems."""
