@@ -22,6 +22,9 @@
  *                           argmin)
  *   mvn_v2v_front        <- mvn/models/v2v.py:7-17, 145-146 (V2VModel.front_layers[0] =
  *                           Basic3DBlock(32, 16, 7), eval mode; BASELINE config 5)
+ *   mvn_triangulate_ransac <- mvn/models/triangulation.py:54-128 (the RANSAC baseline's host
+ *                           loop: hypotheses, inlier DLT, Huber refinement)
+ *   mvn_reprojection_error <- mvn/utils/multiview.py:177-184 calc_reprojection_error_matrix(...)
  *
  * Conventions
  *   - Every buffer is caller-owned device memory (hipMalloc / torch), contiguous,
@@ -332,6 +335,52 @@ int mvn_softargmax3d_backward(const void* vol, int vol_dtype, int64_t vol_bstrid
  */
 int mvn_dlt_backward(const float* proj, const float* pts, const float* conf, const float* grad_out,
                      float* grad_pts, float* grad_conf, int B, int N, int J, void* stream);
+
+/*
+ * Batched reprojection error.  Replaces mvn/utils/multiview.py:177-184
+ * (calc_reprojection_error_matrix): HALF the Euclidean pixel distance between each 2D point
+ * and the projection of its 3D point, f64 arithmetic.
+ *
+ *   points3d (B, J, 3)    f32
+ *   pts      (B, N, J, 2) f32     2D points, pixels
+ *   proj     (B, N, 3, 4) f32
+ *   out      (B, J, N)    f32
+ *
+ * MVN_ERR_ARG for a null pointer, MVN_ERR_SHAPE for a non-positive or too large extent.
+ */
+int mvn_reprojection_error(const float* points3d, const float* pts, const float* proj,
+                           float* out, int B, int N, int J, void* stream);
+
+/*
+ * RANSAC triangulation of a batch of points with Huber refinement.  Replaces the host loop
+ * of mvn/models/triangulation.py:54-128 (RANSACTriangulationNet.triangulate_ransac over
+ * B x J).  For each (b, j): every entry i < n_iters of the caller's list of view pairs is a
+ * hypothesis -- the unweighted two-view DLT point (f64, multiview.py:119-127), whose inliers
+ * are the pair itself and every view with reprojection error < epsilon (strict; a NaN error
+ * is no inlier).  A pair with an index outside [0, N) or two equal indices is skipped and
+ * never read through.  The hypothesis with the most inliers wins, the lowest i on a tie
+ * (triangulation.py:96-97); with no valid pair all views are used (:100-101).  The result
+ * is the unweighted DLT over the inlier views and, with direct_optimization = 1, the
+ * minimiser of the reference's cost 1/2 sum rho(r_v^2) over them (r_v the half pixel
+ * distance, rho scipy's Huber with f_scale 1) by a damped Gauss-Newton iteration in f64
+ * that starts at the DLT point and accepts no step that raises the cost.
+ *
+ *   proj   (B, N, 3, 4) f32,  pts (B, N, J, 2) f32,  2 <= N <= 32
+ *   pairs  int32: pairs_per_point = 0: (n_iters, 2), one list for every point;
+ *                 pairs_per_point = 1: (B, J, n_iters, 2);  1 <= n_iters <= 4096
+ *   out_xyz        (B, J, 3) f32
+ *   out_inliers    (B, J)    u32   bit v set: view v was used
+ *   out_error_mean (B, J)    f32   mean reprojection error over the inlier views at the
+ *                                  returned point (triangulation.py:125-126); may be NULL
+ *
+ * Stream-ordered, allocates nothing, keeps no state.  MVN_ERR_ARG for a null pointer or a
+ * flag other than 0 / 1; MVN_ERR_SHAPE for N < 2, N > 32, n_iters < 1, n_iters > 4096 or a
+ * non-positive or too large extent.  Checked before any HIP call.
+ */
+int mvn_triangulate_ransac(const float* proj, const float* pts, const int32_t* pairs,
+                           int pairs_per_point, int n_iters, float epsilon, int direct_optimization,
+                           float* out_xyz, uint32_t* out_inliers, float* out_error_mean,
+                           int B, int N, int J, void* stream);
 
 /*
  * Test hook (tests only; process-wide, thread-safe): force unprojection code paths.

@@ -250,3 +250,52 @@ def dlt(proj: Tensor, pts: Tensor, conf: Optional[Tensor]) -> Tensor:
 def _(proj, pts, conf):
     B, N, J = pts.shape[:3]
     return pts.new_empty((B, J, 3), dtype=torch.float32)
+
+
+# --------------------------------------------------------------------------- RANSAC
+@_op("reprojection_error")
+def reprojection_error(points3d: Tensor, pts: Tensor, proj: Tensor) -> Tensor:
+    """points3d (B,J,3) f32, pts (B,N,J,2) f32, proj (B,N,3,4) f32 -> (B,J,N) f32, half the
+    pixel distance (multiview.py:177-184)."""
+    _require_gpu(points3d, pts, proj)
+    B, N, J = pts.shape[:3]
+    out = torch.empty((B, J, N), dtype=torch.float32, device=pts.device)
+    if out.numel() == 0:
+        return out
+    code = _lib.load().mvn_reprojection_error(points3d.data_ptr(), pts.data_ptr(), proj.data_ptr(),
+                                              out.data_ptr(), B, N, J, _stream(pts))
+    _lib.check(code, "mvn_reprojection_error")
+    return out
+
+
+@reprojection_error.register_fake
+def _(points3d, pts, proj):
+    B, N, J = pts.shape[:3]
+    return pts.new_empty((B, J, N), dtype=torch.float32)
+
+
+@_op("ransac")
+def ransac(proj: Tensor, pts: Tensor, pairs: Tensor, epsilon: float,
+           direct_optimization: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """proj (B,N,3,4) f32, pts (B,N,J,2) f32, pairs int32 (n_iters,2) or (B,J,n_iters,2)
+    -> (xyz (B,J,3) f32, inlier masks (B,J) int32 (bit v: view v used), mean error (B,J) f32)."""
+    _require_gpu(proj, pts, pairs)
+    B, N, J = pts.shape[:3]
+    xyz = torch.empty((B, J, 3), dtype=torch.float32, device=pts.device)
+    mask = torch.empty((B, J), dtype=torch.int32, device=pts.device)
+    err = torch.empty((B, J), dtype=torch.float32, device=pts.device)
+    if mask.numel() == 0:
+        return xyz, mask, err
+    code = _lib.load().mvn_triangulate_ransac(proj.data_ptr(), pts.data_ptr(), pairs.data_ptr(),
+                                              int(pairs.dim() == 4), pairs.shape[-2], float(epsilon),
+                                              int(direct_optimization), xyz.data_ptr(), mask.data_ptr(),
+                                              err.data_ptr(), B, N, J, _stream(pts))
+    _lib.check(code, "mvn_triangulate_ransac")
+    return xyz, mask, err
+
+
+@ransac.register_fake
+def _(proj, pts, pairs, epsilon, direct_optimization):
+    B, N, J = pts.shape[:3]
+    return (pts.new_empty((B, J, 3), dtype=torch.float32), pts.new_empty((B, J), dtype=torch.int32),
+            pts.new_empty((B, J), dtype=torch.float32))
