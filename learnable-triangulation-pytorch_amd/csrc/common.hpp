@@ -84,7 +84,7 @@ inline bool launch_ok() { return hipGetLastError() == hipSuccess; }
 // checks it after every GPU test when the debug library is loaded).  Release builds compile the
 // checks away.
 using DassertReader = int (*)(unsigned* count, unsigned* line);
-std::vector<DassertReader>& dassert_registry();      // defined in unproject.hip
+std::vector<DassertReader>& dassert_registry();      // defined in debug.hip
 #ifdef MVN_DEVICE_ASSERTS
 namespace {
 __device__ unsigned g_dassert[2];                    // failures, first failing line (this unit)
@@ -114,7 +114,7 @@ const bool g_dassert_registered = (dassert_registry().push_back(&dassert_read_cl
   } while (0)
 #endif
 
-// Test-only knobs of the unprojection dispatch (mvn_debug_set_unproject, unproject.hip):
+// Test-only knobs of the unprojection dispatch (mvn_debug_set_unproject, debug.hip):
 // process-wide atomics set by tests to force the multi-pass / global-gather / simple
 // kernel paths; nothing is read from the environment on the launch path.
 int unproject_lds_slot_budget();   // 0 = the kernel's own budget

@@ -14,10 +14,6 @@
 //   sampling    fma(v_se,se, fma(v_sw,sw, fma(v_ne,ne, v_nw*nw)))  (ATen CPU grid sampler, §8a a1.5)
 // so 'sum' / 'max' / 'conf' are bit-exact with the torch CPU reference and
 // 'softmax' differs only by exp() rounding (<= 1e-6 rel).
-#include <stdlib.h>
-
-#include <atomic>
-
 #include "unproject_common.hpp"
 
 namespace mvn {
@@ -54,36 +50,8 @@ __global__ __launch_bounds__(kUnprojBlock) void unproject_regviews(
     for (int v = 0; v < kMaxRegViews; ++v)
       if (v < N) s[v] = sample(fb + (size_t(v) * C + c) * HW, t[v]);
 
-    float r;
-    if constexpr (AGG == MVN_AGG_SUM) {            // op.py:150, sequential over views
-      r = s[0];
-#pragma unroll
-      for (int v = 1; v < kMaxRegViews; ++v) if (v < N) r = r + s[v];
-    } else if constexpr (AGG == MVN_AGG_MAX) {     // op.py:152
-      r = s[0];
-#pragma unroll
-      for (int v = 1; v < kMaxRegViews; ++v) if (v < N) r = max_takes(s[v], r) ? s[v] : r;
-    } else if constexpr (AGG == MVN_AGG_CONF) {    // op.py:148: product rounded, then summed
-      const float* cf = conf + size_t(b) * N * C + c;
-      r = s[0] * cf[0];
-#pragma unroll
-      for (int v = 1; v < kMaxRegViews; ++v) if (v < N) r = r + s[v] * cf[size_t(v) * C];
-    } else {                                       // op.py:153-159, softmax over views
-      float m = s[0];
-#pragma unroll
-      for (int v = 1; v < kMaxRegViews; ++v) if (v < N) m = fmaxf(m, s[v]);
-      const float ml = m * kLog2e;
-      float den = 0.f, num = 0.f;
-#pragma unroll
-      for (int v = 0; v < kMaxRegViews; ++v)
-        if (v < N) {
-          const float e = softmax_exp(s[v], ml);
-          den += e;
-          num = __builtin_fmaf(s[v], e, num);
-        }
-      r = num * __builtin_amdgcn_rcpf(den);
-    }
-    store_elem(ob + size_t(c) * nvox, r);
+    const float* cf = AGG == MVN_AGG_CONF ? conf + size_t(b) * N * C + c : nullptr;
+    store_elem(ob + size_t(c) * nvox, aggregate<AGG, kMaxRegViews>(s, N, cf, C));
   }
 }
 
@@ -134,59 +102,26 @@ __global__ __launch_bounds__(kUnprojBlock) void unproject_anyviews(
 // Kernel choice: the tiled LDS-staged kernel (unproject_tiled.hip) for N <= 8 views, the
 // register-geometry kernel above when a test forces it (mvn_debug_set_unproject), and the
 // any-N kernel for more than 8 views.
-inline bool use_simple_kernel() { return unproject_force_simple(); }
-
 template <int AGG, typename TIn, typename TOut>
-int launch_agg(const void* feat, const float* P, const float* coords, const float* cub, int transfer,
-               const float* conf, void* out, int B, int N, int C, int H, int W, int Vx, int Vy, int Vz,
-               int align_corners, int out_cl, int fast, hipStream_t s) {
-  const int nvox = Vx * Vy * Vz;
-  if (N <= kMaxRegViews && !use_simple_kernel())
-    return launch_tiled<AGG, TIn, TOut>(feat, P, coords, cub, transfer, conf, out, B, N, C, H, W, Vx, Vy, Vz,
-                                        align_corners, out_cl, fast, s);
-  if (cub) return MVN_ERR_SHAPE;     // in-kernel coordinates: the tiled kernel only (N <= 8)
-  if (out_cl) return MVN_ERR_ARG;    // channels-last output: the tiled kernel only (N <= 8)
-  dim3 grid((nvox + kUnprojBlock - 1) / kUnprojBlock, B);
-  if (N <= kMaxRegViews)
-    unproject_regviews<AGG, TIn, TOut><<<grid, kUnprojBlock, 0, s>>>(
-        static_cast<const TIn*>(feat), P, coords, conf, static_cast<TOut*>(out), N, C, H, W, nvox,
-        align_corners);
-  else
-    unproject_anyviews<AGG, TIn, TOut><<<grid, kUnprojBlock, 0, s>>>(
-        static_cast<const TIn*>(feat), P, coords, conf, static_cast<TOut*>(out), N, C, H, W, nvox,
-        align_corners);
+int launch_agg(const UnprojCall& c) {
+  if (c.N <= kMaxRegViews && !unproject_force_simple()) return launch_tiled<AGG, TIn, TOut>(c);
+  if (c.cub) return MVN_ERR_SHAPE;     // in-kernel coordinates: the tiled kernel only (N <= 8)
+  if (c.out_cl) return MVN_ERR_ARG;    // channels-last output: the tiled kernel only (N <= 8)
+  const int nvox = c.Vx * c.Vy * c.Vz;
+  const dim3 grid((nvox + kUnprojBlock - 1) / kUnprojBlock, c.B);
+  const auto kernel = c.N <= kMaxRegViews ? unproject_regviews<AGG, TIn, TOut> : unproject_anyviews<AGG, TIn, TOut>;
+  kernel<<<grid, kUnprojBlock, 0, c.s>>>(static_cast<const TIn*>(c.feat), c.P, c.coords, c.conf,
+                                         static_cast<TOut*>(c.out), c.N, c.C, c.H, c.W, nvox, c.align_corners);
   return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
 }
 
-template <typename TIn, typename TOut>
-int launch_types(int agg, const void* feat, const float* P, const float* coords, const float* cub, int transfer,
-                 const float* conf, void* out, int B, int N, int C, int H, int W, int Vx, int Vy, int Vz,
-                 int align_corners, int out_cl, int fast, hipStream_t s) {
-  switch (agg) {
-    case MVN_AGG_SUM:
-      return launch_agg<MVN_AGG_SUM, TIn, TOut>(feat, P, coords, cub, transfer, conf, out, B, N, C, H, W, Vx, Vy, Vz, align_corners, out_cl, fast, s);
-    case MVN_AGG_MAX:
-      return launch_agg<MVN_AGG_MAX, TIn, TOut>(feat, P, coords, cub, transfer, conf, out, B, N, C, H, W, Vx, Vy, Vz, align_corners, out_cl, fast, s);
-    case MVN_AGG_SOFTMAX:
-      return launch_agg<MVN_AGG_SOFTMAX, TIn, TOut>(feat, P, coords, cub, transfer, conf, out, B, N, C, H, W, Vx, Vy, Vz, align_corners, out_cl, fast, s);
-    case MVN_AGG_CONF:
-      return launch_agg<MVN_AGG_CONF, TIn, TOut>(feat, P, coords, cub, transfer, conf, out, B, N, C, H, W, Vx, Vy, Vz, align_corners, out_cl, fast, s);
-  }
-  return MVN_ERR_ARG;
-}
-
-}  // namespace
-}  // namespace mvn
-
-namespace mvn {
-namespace {
+// Validation common to the public entry points, then the dtype and aggregation dispatch.
 int unproject_entry(const void* feat, int feat_dtype, const float* proj, const float* coords, const float* cub,
                     int transfer, const float* conf, void* out, int out_dtype, int out_layout, int B, int N, int C,
                     int H, int W, int Vx, int Vy, int Vz, int agg, int align_corners, int precision,
                     void* stream) {
   if (!feat || !proj || !(coords || cub) || !out) return MVN_ERR_ARG;
   if (precision != MVN_PRECISION_EXACT && precision != MVN_PRECISION_FAST) return MVN_ERR_ARG;
-  const int fast = precision == MVN_PRECISION_FAST;
   if (agg < MVN_AGG_SUM || agg > MVN_AGG_CONF) return MVN_ERR_ARG;
   if (agg == MVN_AGG_CONF && !conf) return MVN_ERR_ARG;
   if (align_corners != 0 && align_corners != 1) return MVN_ERR_ARG;
@@ -195,85 +130,22 @@ int unproject_entry(const void* feat, int feat_dtype, const float* proj, const f
   if (B <= 0 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || Vx <= 0 || Vy <= 0 || Vz <= 0) return MVN_ERR_SHAPE;
   const long long nvox = (long long)Vx * Vy * Vz;
   if (nvox > (1LL << 30) || (long long)H * W > (1LL << 30) || B > 65535) return MVN_ERR_SHAPE;
-  const int cl = out_layout == MVN_LAYOUT_NDHWC;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (feat_dtype == MVN_DTYPE_F32 && out_dtype == MVN_DTYPE_F32)
-    return launch_types<float, float>(agg, feat, proj, coords, cub, transfer, conf, out, B, N, C, H, W, Vx, Vy, Vz,
-                                      align_corners, cl, fast, s);
-  if (feat_dtype == MVN_DTYPE_BF16 && out_dtype == MVN_DTYPE_BF16)
-    return launch_types<uint16_t, uint16_t>(agg, feat, proj, coords, cub, transfer, conf, out, B, N, C, H, W, Vx, Vy,
-                                            Vz, align_corners, cl, fast, s);
-  if (feat_dtype == MVN_DTYPE_BF16 && out_dtype == MVN_DTYPE_F32)
-    return launch_types<uint16_t, float>(agg, feat, proj, coords, cub, transfer, conf, out, B, N, C, H, W, Vx, Vy, Vz,
-                                         align_corners, cl, fast, s);
-  return MVN_ERR_DTYPE;
+  UnprojCall c;
+  c.feat = feat; c.P = proj; c.coords = coords; c.cub = cub; c.transfer = transfer; c.conf = conf; c.out = out;
+  c.B = B; c.N = N; c.C = C; c.H = H; c.W = W; c.Vx = Vx; c.Vy = Vy; c.Vz = Vz;
+  c.align_corners = align_corners;
+  c.out_cl = out_layout == MVN_LAYOUT_NDHWC;
+  c.fast = precision == MVN_PRECISION_FAST;
+  c.s = static_cast<hipStream_t>(stream);
+  return with_dtypes<false>(feat_dtype, out_dtype, [&](auto tin, auto tout) {
+    return with_agg(agg, [&](auto a) {
+      return launch_agg<decltype(a)::value, typename decltype(tin)::type, typename decltype(tout)::type>(c);
+    });
+  });
 }
+
 }  // namespace
 }  // namespace mvn
-
-namespace mvn {
-namespace {
-std::atomic<int> g_lds_slots{0}, g_force_simple{0};
-}  // namespace
-int unproject_lds_slot_budget() { return g_lds_slots.load(std::memory_order_relaxed); }
-bool unproject_force_simple() { return g_force_simple.load(std::memory_order_relaxed) == 1; }
-bool unproject_force_generic() { return g_force_simple.load(std::memory_order_relaxed) == 2; }
-}  // namespace mvn
-
-namespace mvn {
-namespace unproj {
-int x4_blocks_per_cu(int bf16);
-}  // namespace unproj
-}  // namespace mvn
-
-extern "C" int mvn_debug_unproject_occupancy(int bf16_maps) {
-  return mvn::unproj::x4_blocks_per_cu(bf16_maps ? 1 : 0);
-}
-
-namespace mvn {
-std::vector<DassertReader>& dassert_registry() {
-  static std::vector<DassertReader> r;
-  return r;
-}
-}  // namespace mvn
-
-namespace mvn {
-namespace {
-// one deliberately failing check per lane >= n (the mechanism's self-test)
-__global__ void dassert_selftest(int n) { MVN_DASSERT(int(threadIdx.x) < n); }
-}  // namespace
-}  // namespace mvn
-
-extern "C" int mvn_debug_dassert_selftest(int n, void* stream) {
-  if (n < 0 || n > 64) return MVN_ERR_ARG;
-  mvn::dassert_selftest<<<1, 64, 0, static_cast<hipStream_t>(stream)>>>(n);
-  return mvn::launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
-}
-
-extern "C" int mvn_debug_device_asserts(int* enabled, unsigned* count, unsigned* first_line) {
-  if (!enabled || !count || !first_line) return MVN_ERR_ARG;
-#ifdef MVN_DEVICE_ASSERTS
-  *enabled = 1;
-#else
-  *enabled = 0;
-#endif
-  *count = 0;
-  *first_line = 0;
-  for (auto rd : mvn::dassert_registry()) {
-    unsigned c = 0, l = 0;
-    if (rd(&c, &l) != 0) return MVN_ERR_LAUNCH;
-    if (c && !*count) *first_line = l;
-    *count += c;
-  }
-  return MVN_OK;
-}
-
-extern "C" int mvn_debug_set_unproject(int lds_slots, int kernel) {
-  if (lds_slots < 0 || kernel < 0 || kernel > 2) return MVN_ERR_ARG;
-  mvn::g_lds_slots.store(lds_slots, std::memory_order_relaxed);
-  mvn::g_force_simple.store(kernel, std::memory_order_relaxed);
-  return MVN_OK;
-}
 
 extern "C" int mvn_unproject_ex(const void* feat, int feat_dtype, const float* proj, const float* coords,
                                 const float* conf, void* out, int out_dtype, int out_layout, int B, int N, int C,

@@ -522,71 +522,50 @@ __global__ void fix_to_f32(const unsigned long long* __restrict__ q, const unsig
   }
 }
 
+// One backward call as the entry points received it (validated by check_bwd_args); fa: the
+// fixed-point outputs (DET), else empty.
+struct BwdCall {
+  const void* feat;
+  int feat_dtype;
+  const float *P, *coords, *conf;
+  const void* gout;
+  int gout_dtype;
+  float *gfeat, *gconf;
+  FixArgs fa;
+  int B, N, C, H, W, Vx, Vy, Vz;
+  int agg, align_corners;
+  hipStream_t s;
+};
+
 template <int AGG, typename TIn, typename TG, bool DET>
-int launch_bwd(const void* feat, const float* P, const float* coords, const float* conf, const void* gout, float* gfeat,
-               float* gconf, FixArgs fa, int B, int N,
-               int C, int H, int W, int Vx, int Vy, int Vz, int ac, hipStream_t s) {
-  const long long nb = (long long)B * ((Vx + TX - 1) / TX) * ((Vy + TY - 1) / TY) * ((Vz + TZ - 1) / TZ);
-  if (nb > INT_MAX) return MVN_ERR_SHAPE;
-  if (N <= 4)
-    unproject_bwd_tiled<AGG, TIn, TG, 4, DET><<<int(nb), kThreads, 0, s>>>(static_cast<const TIn*>(feat), P, coords,
-        conf, static_cast<const TG*>(gout), gfeat, gconf, fa, B, N, C, H, W, Vx, Vy, Vz, ac);
-  else if (N <= 8)
-    unproject_bwd_tiled<AGG, TIn, TG, 8, DET><<<int(nb), kThreads, 0, s>>>(static_cast<const TIn*>(feat), P, coords,
-        conf, static_cast<const TG*>(gout), gfeat, gconf, fa, B, N, C, H, W, Vx, Vy, Vz, ac);
-  else
-    return MVN_ERR_SHAPE;
+int launch_bwd(const BwdCall& c) {
+  const long long nb = tile_blocks(c.B, c.Vx, c.Vy, c.Vz, TX, TY, TZ);
+  if (nb > INT_MAX || c.N > 8) return MVN_ERR_SHAPE;
+  const auto kernel = c.N <= 4 ? unproject_bwd_tiled<AGG, TIn, TG, 4, DET> : unproject_bwd_tiled<AGG, TIn, TG, 8, DET>;
+  kernel<<<int(nb), kThreads, 0, c.s>>>(static_cast<const TIn*>(c.feat), c.P, c.coords, c.conf,
+                                        static_cast<const TG*>(c.gout), c.gfeat, c.gconf, c.fa, c.B, c.N, c.C, c.H,
+                                        c.W, c.Vx, c.Vy, c.Vz, c.align_corners);
   return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
 }
 
-template <typename TIn, typename TG, bool DET>
-int dispatch_bwd(int agg, const void* feat, const float* P, const float* coords, const float* conf, const void* gout,
-                 float* gfeat, float* gconf, FixArgs fa,
-                 int B, int N, int C, int H, int W, int Vx, int Vy, int Vz, int ac, hipStream_t s) {
-  switch (agg) {
-    case MVN_AGG_SUM:
-      return launch_bwd<MVN_AGG_SUM, TIn, TG, DET>(feat, P, coords, conf, gout, gfeat, gconf, fa, B, N, C, H,
-                                                   W, Vx, Vy, Vz, ac, s);
-    case MVN_AGG_MAX:
-      return launch_bwd<MVN_AGG_MAX, TIn, TG, DET>(feat, P, coords, conf, gout, gfeat, gconf, fa, B, N, C, H,
-                                                   W, Vx, Vy, Vz, ac, s);
-    case MVN_AGG_SOFTMAX:
-      return launch_bwd<MVN_AGG_SOFTMAX, TIn, TG, DET>(feat, P, coords, conf, gout, gfeat, gconf, fa, B, N,
-                                                       C, H, W, Vx, Vy, Vz, ac, s);
-    case MVN_AGG_CONF:
-      return launch_bwd<MVN_AGG_CONF, TIn, TG, DET>(feat, P, coords, conf, gout, gfeat, gconf, fa, B, N, C,
-                                                    H, W, Vx, Vy, Vz, ac, s);
-  }
-  return MVN_ERR_ARG;
-}
-
 template <bool DET>
-int backward_entry(const void* feat, int feat_dtype, const float* proj, const float* coords, const float* conf,
-                   const void* grad_out, int grad_out_dtype, float* grad_feat, float* grad_conf,
-                   FixArgs fa, int B, int N, int C, int H,
-                   int W, int Vx, int Vy, int Vz, int agg, int align_corners, hipStream_t s) {
-  const bool f16 = feat_dtype == MVN_DTYPE_BF16, g16 = grad_out_dtype == MVN_DTYPE_BF16;
-  if ((feat_dtype != MVN_DTYPE_F32 && !f16) || (grad_out_dtype != MVN_DTYPE_F32 && !g16)) return MVN_ERR_DTYPE;
-  if (!f16 && !g16)
-    return dispatch_bwd<float, float, DET>(agg, feat, proj, coords, conf, grad_out, grad_feat, grad_conf, fa,
-                                           B, N, C, H, W, Vx, Vy, Vz, align_corners, s);
-  if (f16 && g16)
-    return dispatch_bwd<uint16_t, uint16_t, DET>(agg, feat, proj, coords, conf, grad_out, grad_feat, grad_conf, fa, B, N, C, H, W, Vx, Vy, Vz, align_corners, s);
-  if (f16)
-    return dispatch_bwd<uint16_t, float, DET>(agg, feat, proj, coords, conf, grad_out, grad_feat, grad_conf, fa, B, N, C, H, W, Vx, Vy, Vz, align_corners, s);
-  return dispatch_bwd<float, uint16_t, DET>(agg, feat, proj, coords, conf, grad_out, grad_feat, grad_conf, fa,
-                                            B, N, C, H, W, Vx, Vy, Vz, align_corners, s);
+int backward_entry(const BwdCall& c) {
+  return with_dtypes<true>(c.feat_dtype, c.gout_dtype, [&](auto tin, auto tg) {
+    return with_agg(c.agg, [&](auto a) {
+      return launch_bwd<decltype(a)::value, typename decltype(tin)::type, typename decltype(tg)::type, DET>(c);
+    });
+  });
 }
 
-int check_bwd_args(const void* feat, const float* proj, const float* coords, const float* conf, const void* grad_out,
-                   const float* grad_feat, int B, int N, int C, int H, int W, int Vx, int Vy, int Vz, int agg,
-                   int align_corners) {
-  if (!feat || !proj || !coords || !grad_out || !grad_feat) return MVN_ERR_ARG;
-  if (agg < MVN_AGG_SUM || agg > MVN_AGG_CONF) return MVN_ERR_ARG;
-  if (agg == MVN_AGG_CONF && !conf) return MVN_ERR_ARG;
-  if (align_corners != 0 && align_corners != 1) return MVN_ERR_ARG;
-  if (B <= 0 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || Vx <= 0 || Vy <= 0 || Vz <= 0) return MVN_ERR_SHAPE;
-  if ((long long)Vx * Vy * Vz > (1LL << 30) || (long long)H * W > (1LL << 30) || N > 8) return MVN_ERR_SHAPE;
+int check_bwd_args(const BwdCall& c) {
+  if (!c.feat || !c.P || !c.coords || !c.gout || !c.gfeat) return MVN_ERR_ARG;
+  if (c.agg < MVN_AGG_SUM || c.agg > MVN_AGG_CONF) return MVN_ERR_ARG;
+  if (c.agg == MVN_AGG_CONF && !c.conf) return MVN_ERR_ARG;
+  if (c.align_corners != 0 && c.align_corners != 1) return MVN_ERR_ARG;
+  if (c.B <= 0 || c.N <= 0 || c.C <= 0 || c.H <= 0 || c.W <= 0 || c.Vx <= 0 || c.Vy <= 0 || c.Vz <= 0)
+    return MVN_ERR_SHAPE;
+  if ((long long)c.Vx * c.Vy * c.Vz > (1LL << 30) || (long long)c.H * c.W > (1LL << 30) || c.N > 8)
+    return MVN_ERR_SHAPE;
   return MVN_OK;
 }
 
@@ -598,14 +577,11 @@ extern "C" int mvn_unproject_backward(const void* feat, int feat_dtype, const fl
                                       const float* conf, const void* grad_out, int grad_out_dtype, float* grad_feat,
                                       float* grad_conf, int B, int N, int C, int H, int W, int Vx, int Vy, int Vz,
                                       int agg, int align_corners, void* stream) {
-  using namespace mvn;
   using namespace mvn::unproj;
-  const int e = check_bwd_args(feat, proj, coords, conf, grad_out, grad_feat, B, N, C, H, W, Vx, Vy, Vz, agg,
-                               align_corners);
-  if (e != MVN_OK) return e;
-  return backward_entry<false>(feat, feat_dtype, proj, coords, conf, grad_out, grad_out_dtype, grad_feat, grad_conf,
-                               FixArgs{}, B, N, C, H, W, Vx, Vy, Vz, agg, align_corners,
-                               static_cast<hipStream_t>(stream));
+  const BwdCall c{feat, feat_dtype, proj, coords, conf, grad_out, grad_out_dtype, grad_feat, grad_conf, FixArgs{},
+                  B, N, C, H, W, Vx, Vy, Vz, agg, align_corners, static_cast<hipStream_t>(stream)};
+  const int e = check_bwd_args(c);
+  return e != MVN_OK ? e : backward_entry<false>(c);
 }
 
 extern "C" size_t mvn_unproject_backward_workspace_bytes(int B, int N, int C, int H, int W) {
@@ -625,12 +601,13 @@ extern "C" int mvn_unproject_backward_deterministic(const void* feat, int feat_d
                                                     void* stream) {
   using namespace mvn;
   using namespace mvn::unproj;
-  const int e = check_bwd_args(feat, proj, coords, conf, grad_out, grad_feat, B, N, C, H, W, Vx, Vy, Vz, agg,
-                               align_corners);
+  BwdCall c{feat, feat_dtype, proj, coords, conf, grad_out, grad_out_dtype, grad_feat, grad_conf, FixArgs{},
+            B, N, C, H, W, Vx, Vy, Vz, agg, align_corners, static_cast<hipStream_t>(stream)};
+  const int e = check_bwd_args(c);
   if (e != MVN_OK) return e;
   const size_t nfeat = size_t(B) * N * C * size_t(H) * W, nconf = size_t(B) * N * C;
   if (!workspace || workspace_bytes < mvn_unproject_backward_workspace_bytes(B, N, C, H, W)) return MVN_ERR_WORKSPACE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = c.s;
   const size_t planes = size_t(B) * C;
   char* ws = static_cast<char*>(workspace);
   auto* scale = reinterpret_cast<float*>(ws + kFixHeaderBytes);
@@ -644,24 +621,15 @@ extern "C" int mvn_unproject_backward_deterministic(const void* feat, int feat_d
   // the fixed-point scale of each (frame, channel) plane from its finite maxima (device-side)
   if (planes > INT_MAX) return MVN_ERR_SHAPE;
   const int nvox = Vx * Vy * Vz, HW = H * W;
-  const bool f16 = feat_dtype == MVN_DTYPE_BF16, g16 = grad_out_dtype == MVN_DTYPE_BF16;
-  if ((feat_dtype != MVN_DTYPE_F32 && !f16) || (grad_out_dtype != MVN_DTYPE_F32 && !g16)) return MVN_ERR_DTYPE;
-  const int nb = int(planes);
-  if (f16 && g16)
-    fix_scale_planes<<<nb, 256, 0, s>>>(static_cast<const uint16_t*>(feat), static_cast<const uint16_t*>(grad_out), conf,
-                                        scale, expo, N, C, HW, nvox, agg);
-  else if (f16)
-    fix_scale_planes<<<nb, 256, 0, s>>>(static_cast<const uint16_t*>(feat), static_cast<const float*>(grad_out), conf,
-                                        scale, expo, N, C, HW, nvox, agg);
-  else if (g16)
-    fix_scale_planes<<<nb, 256, 0, s>>>(static_cast<const float*>(feat), static_cast<const uint16_t*>(grad_out), conf,
-                                        scale, expo, N, C, HW, nvox, agg);
-  else
-    fix_scale_planes<<<nb, 256, 0, s>>>(static_cast<const float*>(feat), static_cast<const float*>(grad_out), conf,
-                                        scale, expo, N, C, HW, nvox, agg);
-  const int r = backward_entry<true>(feat, feat_dtype, proj, coords, conf, grad_out, grad_out_dtype, grad_feat,
-                                     grad_conf, FixArgs{qfeat, qconf, ffeat, fconf, scale}, B, N, C, H, W, Vx,
-                                     Vy, Vz, agg, align_corners, s);
+  int r = with_dtypes<true>(feat_dtype, grad_out_dtype, [&](auto tin, auto tg) {
+    fix_scale_planes<<<int(planes), 256, 0, s>>>(static_cast<const typename decltype(tin)::type*>(feat),
+                                                 static_cast<const typename decltype(tg)::type*>(grad_out), conf,
+                                                 scale, expo, N, C, HW, nvox, agg);
+    return MVN_OK;
+  });
+  if (r != MVN_OK) return r;
+  c.fa = FixArgs{qfeat, qconf, ffeat, fconf, scale};
+  r = backward_entry<true>(c);
   if (r != MVN_OK) return r;
   auto cvt_blocks = [](size_t n) { return int(std::min<size_t>((n + 255) / 256, 65536)); };
   fix_to_f32<<<cvt_blocks(nfeat), 256, 0, s>>>(qfeat, ffeat, grad_feat, nfeat, expo, C, size_t(HW), size_t(N) * C * HW);

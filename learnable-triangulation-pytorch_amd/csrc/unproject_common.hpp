@@ -1,7 +1,9 @@
-// Shared device code of the unprojection kernels (unproject.hip, unproject_tiled.hip).
+// Shared code of the unprojection kernels (unproject.hip, unproject_tiled.hip, unproject_x4.hip,
+// unproject_bwd.hip): device helpers first, the host-side call record and dispatch helpers last.
 #pragma once
 
 #include <climits>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -9,11 +11,13 @@ namespace mvn {
 namespace unproj {
 
 // ---- the one f32 form of the cross-view softmax (op.py:153-159) ----------------------
-// Every unprojection path — the staged LDS paths, the global-gather fallback, the simple
-// kernels and the backward — evaluates it the same way, so a tensor never mixes two
-// roundings (which path a tile takes depends on LDS budget and camera distance):
+// Every unprojection path for up to 8 views — the staged LDS paths, the global-gather fallback,
+// the register-geometry kernel and the backward — evaluates it the same way, so a tensor never
+// mixes two roundings (which path a tile takes depends on LDS budget and camera distance):
 //   m = max_v s_v;  e_v = exp2(fma(s_v, log2 e, -(m * log2 e)));  den = ((e_0 + e_1) + ...);
 //   value = fma chain of s_v * e_v, times rcp(den).   (<= 1e-5 of the reference's softmax)
+// The exception is the any-N kernel (unproject_anyviews, more than 8 views), which keeps an
+// online softmax with __expf and an IEEE division; its whole tensor is computed that one way.
 constexpr float kLog2e = 1.4426950408889634f;
 __device__ __forceinline__ float softmax_exp(float s, float ml) {   // ml = m * kLog2e
   return __builtin_amdgcn_exp2f(__builtin_fmaf(s, kLog2e, -ml));
@@ -40,17 +44,26 @@ struct Proj {
   bool invalid;      // depth <= 0 (op.py:121)
 };
 
+struct Homog {
+  float uh, vh, wh;   // [x y z 1] @ P^T (op.py:117-119 -> multiview.py:96)
+};
+__device__ __forceinline__ Homog homog(const float* __restrict__ Pv, float x, float y, float z) {
+  Homog h;
+  h.uh = __builtin_fmaf(1.f, Pv[3], __builtin_fmaf(z, Pv[2], __builtin_fmaf(y, Pv[1], x * Pv[0])));
+  h.vh = __builtin_fmaf(1.f, Pv[7], __builtin_fmaf(z, Pv[6], __builtin_fmaf(y, Pv[5], x * Pv[4])));
+  h.wh = __builtin_fmaf(1.f, Pv[11], __builtin_fmaf(z, Pv[10], __builtin_fmaf(y, Pv[9], x * Pv[8])));
+  return h;
+}
+
 __device__ __forceinline__ Proj project(const float* __restrict__ Pv, float x, float y, float z, int H, int W,
                                         int align_corners) {
-  // op.py:117-119 -> multiview.py:96   [x y z 1] @ P^T
-  const float uh = __builtin_fmaf(1.f, Pv[3], __builtin_fmaf(z, Pv[2], __builtin_fmaf(y, Pv[1], x * Pv[0])));
-  const float vh = __builtin_fmaf(1.f, Pv[7], __builtin_fmaf(z, Pv[6], __builtin_fmaf(y, Pv[5], x * Pv[4])));
-  float wh = __builtin_fmaf(1.f, Pv[11], __builtin_fmaf(z, Pv[10], __builtin_fmaf(y, Pv[9], x * Pv[8])));
+  const Homog h = homog(Pv, x, y, z);
+  float wh = h.wh;
   Proj p;
   p.invalid = wh <= 0.f;                   // op.py:121, taken before the guard
   if (wh == 0.f) wh = 1.f;                 // op.py:123
-  const float u = uh / wh;                 // multiview.py:75 (IEEE division)
-  const float v = vh / wh;
+  const float u = h.uh / wh;               // multiview.py:75 (IEEE division)
+  const float v = h.vh / wh;
   // op.py:128-129 — x is divided by heatmap_shape[0] (H) and y by [1] (W): reference quirk kept.
   const float gx = 2.f * (u / float(H) - 0.5f);
   const float gy = 2.f * (v / float(W) - 0.5f);
@@ -90,16 +103,6 @@ __device__ __forceinline__ float div_core(float n, Recip q) {
   return __builtin_fmaf(t1, q.r, q1);
 }
 
-struct Homog {
-  float uh, vh, wh;   // [x y z 1] @ P^T (op.py:117-119 -> multiview.py:96)
-};
-__device__ __forceinline__ Homog homog(const float* __restrict__ Pv, float x, float y, float z) {
-  Homog h;
-  h.uh = __builtin_fmaf(1.f, Pv[3], __builtin_fmaf(z, Pv[2], __builtin_fmaf(y, Pv[1], x * Pv[0])));
-  h.vh = __builtin_fmaf(1.f, Pv[7], __builtin_fmaf(z, Pv[6], __builtin_fmaf(y, Pv[5], x * Pv[4])));
-  h.wh = __builtin_fmaf(1.f, Pv[11], __builtin_fmaf(z, Pv[10], __builtin_fmaf(y, Pv[9], x * Pv[8])));
-  return h;
-}
 __device__ __forceinline__ bool div_core_safe(const Homog& h) {
   const float aw = fabsf(h.wh == 0.f ? 1.f : h.wh);
   return aw >= 0x1p-30f && aw <= 0x1p30f && fabsf(h.uh) <= 0x1p60f && fabsf(h.vh) <= 0x1p60f;
@@ -283,14 +286,6 @@ __device__ __forceinline__ void gather_voxel(const TIn* __restrict__ fb, const f
   }
 }
 
-// Launchers (defined in unproject_tiled.hip); return MVN_OK or an error code.
-template <int AGG, typename TIn, typename TOut>
-// cub != nullptr: voxel coordinates formed in-kernel from the per-frame cuboids (coords unused;
-// Vx = Vy = Vz), see cuboid_coord in common.hpp.
-int launch_tiled(const void* feat, const float* P, const float* coords, const float* cub, int transfer,
-                 const float* conf, void* out, int B, int N, int C, int H, int W, int Vx, int Vy, int Vz,
-                 int align_corners, int out_cl, int fast, hipStream_t s);
-
 // ---- helpers of the chunk-staged kernel (unproject_x4.hip) ------------------------------
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -350,7 +345,6 @@ __device__ __forceinline__ f2 aggregate_pair(const f2 (&s)[NV], const f2 (&cf)[N
     for (int v = 1; v < NV; ++v) r = r + s[v] * cf[v];
     return r;
   } else {
-    constexpr float kLog2e = 1.4426950408889634f;
     f2 m = s[0];
 #pragma unroll
     for (int v = 1; v < NV; ++v) {
@@ -443,37 +437,79 @@ struct Region {
   float inv_cw;
 };
 
-// rg[u] for a runtime u, field by field through selects (an indexed copy of the struct
-// array would go through scratch memory).
-// (each operand goes through readfirstlane — a no-op on these uniform values — so that the
-// select is not folded into an indexed load from a stack copy of the array.)
-__device__ __forceinline__ int rfl(int x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ float rfl(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
-template <int NV>
-__device__ __forceinline__ Region pick_region(const Region (&rg)[NV], int u) {
-  Region r;
-  if constexpr (NV == 4) {
-#define MVN_PICK(f) r.f = u == 0 ? rfl(rg[0].f) : u == 1 ? rfl(rg[1].f) : u == 2 ? rfl(rg[2].f) : rfl(rg[3].f)
-    MVN_PICK(x0); MVN_PICK(y0); MVN_PICK(bw); MVN_PICK(bh); MVN_PICK(pitch); MVN_PICK(sbase); MVN_PICK(xa);
-    MVN_PICK(cw); MVN_PICK(cbase); MVN_PICK(pass); MVN_PICK(cend); MVN_PICK(inv_cw);
-#undef MVN_PICK
-  } else {
-#define MVN_PICK(f)                                                   \
-  r.f = rfl(rg[0].f);                                                 \
-  _Pragma("unroll") for (int k = 1; k < NV; ++k) r.f = u == k ? rfl(rg[k].f) : r.f
-    MVN_PICK(x0); MVN_PICK(y0); MVN_PICK(bw); MVN_PICK(bh); MVN_PICK(pitch); MVN_PICK(sbase); MVN_PICK(xa);
-    MVN_PICK(cw); MVN_PICK(cbase); MVN_PICK(pass); MVN_PICK(cend); MVN_PICK(inv_cw);
-#undef MVN_PICK
+// LDS pixel slot of the staged kernels: one pixel's G channels as f32 (16 or 8 bytes; bf16 maps
+// are widened exactly when staged).
+template <int G> struct SlotT;
+template <> struct SlotT<4> { using type = uint4; };
+template <> struct SlotT<2> { using type = uint2; };
+
+// ---- host side ---------------------------------------------------------------------------
+// One validated forward call (filled by unproject_entry, unproject.hip); the launchers unpack it
+// at the <<<>>> site.  cub != nullptr: voxel coordinates formed in-kernel from the per-frame
+// cuboids (coords unused; Vx = Vy = Vz), see cuboid_coord in common.hpp.
+struct UnprojCall {
+  const void* feat;
+  const float *P, *coords, *cub;
+  int transfer;
+  const float* conf;
+  void* out;
+  int B, N, C, H, W, Vx, Vy, Vz;
+  int align_corners, out_cl, fast;
+  hipStream_t s;
+};
+
+// f(std::integral_constant<int, MVN_AGG_*>) for a runtime aggregation; MVN_ERR_ARG if unknown.
+template <typename F>
+int with_agg(int agg, F&& f) {
+  switch (agg) {
+    case MVN_AGG_SUM: return f(std::integral_constant<int, MVN_AGG_SUM>{});
+    case MVN_AGG_MAX: return f(std::integral_constant<int, MVN_AGG_MAX>{});
+    case MVN_AGG_SOFTMAX: return f(std::integral_constant<int, MVN_AGG_SOFTMAX>{});
+    case MVN_AGG_CONF: return f(std::integral_constant<int, MVN_AGG_CONF>{});
   }
-  return r;
+  return MVN_ERR_ARG;
 }
 
-// The chunk-staged kernel for 4 and 8 views (unproject_x4.hip): MVN_OK, an error code, or 1
-// when it does not apply to the call (then launch_tiled runs the generic kernel).
-template <int AGG, typename TIn, typename TOut>
-int launch_x4(const void* feat, const float* P, const float* coords, const float* cub, int transfer,
-              const float* conf, void* out, int B, int N, int C, int H, int W, int Vx, int Vy, int Vz,
-              int align_corners, int out_cl, int fast, hipStream_t s);
+// f(TypeTag<TIn>, TypeTag<TOther>) for the element types of (feature maps, output or output
+// gradient): f32/f32, bf16/bf16, bf16/f32 and, with F32_BF16 (the backward), f32/bf16; bf16 is
+// carried as uint16_t.  Anything else is MVN_ERR_DTYPE.
+template <typename T> struct TypeTag { using type = T; };
+template <bool F32_BF16, typename F>
+int with_dtypes(int feat_dtype, int other_dtype, F&& f) {
+  const bool f32 = feat_dtype == MVN_DTYPE_F32, f16 = feat_dtype == MVN_DTYPE_BF16;
+  const bool o32 = other_dtype == MVN_DTYPE_F32, o16 = other_dtype == MVN_DTYPE_BF16;
+  if (f32 && o32) return f(TypeTag<float>{}, TypeTag<float>{});
+  if (f16 && o16) return f(TypeTag<uint16_t>{}, TypeTag<uint16_t>{});
+  if (f16 && o32) return f(TypeTag<uint16_t>{}, TypeTag<float>{});
+  if constexpr (F32_BF16)
+    if (f32 && o16) return f(TypeTag<float>{}, TypeTag<uint16_t>{});
+  return MVN_ERR_DTYPE;
+}
+
+// Blocks of a launch with one TX x TY x TZ voxel tile per block (callers check it against INT_MAX).
+inline long long tile_blocks(int B, int Vx, int Vy, int Vz, int TX, int TY, int TZ) {
+  return (long long)B * ((Vx + TX - 1) / TX) * ((Vy + TY - 1) / TY) * ((Vz + TZ - 1) / TZ);
+}
+// 32-bit buffer offsets: a frame's maps and volume must stay below 2 GiB.
+template <typename TIn, typename TOut>
+bool frame_fits_32bit(const UnprojCall& c) {
+  return (long long)c.N * c.C * c.H * c.W * sizeof(TIn) < (1LL << 31) &&
+         (long long)c.C * c.Vx * c.Vy * c.Vz * sizeof(TOut) < (1LL << 31);
+}
+// LDS slot budget per pass (clamped in-kernel to the buffer); tests lower it through
+// mvn_debug_set_unproject to force the multi-pass and global-gather paths.
+inline int lds_slot_budget() {
+  const int knob = unproject_lds_slot_budget();
+  return knob > 0 ? knob : 1 << 30;
+}
+
+// Launchers; return MVN_OK or an error code.  launch_tiled (unproject_tiled.hip) serves every
+// call with N <= 8 views: it tries launch_x4 (unproject_x4.hip: the chunk-staged kernel for 4
+// and 8 views), which returns 1 when it does not apply, and then runs the generic tiled kernel.
+template <int AGG, typename TIn, typename TOut> int launch_tiled(const UnprojCall& c);
+template <int AGG, typename TIn, typename TOut> int launch_x4(const UnprojCall& c);
+// Diagnostics (mvn_debug_unproject_occupancy): resident blocks per CU of the softmax kernels.
+int x4_blocks_per_cu(int bf16);
 
 }  // namespace unproj
 }  // namespace mvn

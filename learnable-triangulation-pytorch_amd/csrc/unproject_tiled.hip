@@ -75,12 +75,9 @@ template <> __device__ __forceinline__ void buf_store<uint16_t>(float x, __amdgp
   __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, static_cast<__bf16>(x)), r, v, s, 0);
 }
 
-// LDS slots hold G f32 channels whatever the input dtype (G = 4: 16-byte slots; G = 2:
+// LDS slots (SlotT) hold G f32 channels whatever the input dtype (G = 4: 16-byte slots; G = 2:
 // 8-byte slots, half the LDS per block, so that two 8-view blocks share a CU): bf16 maps
 // are widened once when staged (each staged pixel is read ~7 times by the taps), not per tap.
-template <int G> struct SlotT;
-template <> struct SlotT<4> { using type = uint4; };
-template <> struct SlotT<2> { using type = uint2; };
 __device__ __forceinline__ void unpack(const uint4& q, float (&v)[4]) {
   v[0] = __uint_as_float(q.x); v[1] = __uint_as_float(q.y); v[2] = __uint_as_float(q.z); v[3] = __uint_as_float(q.w);
 }
@@ -94,30 +91,6 @@ template <typename TIn> __device__ __forceinline__ uint4 pack(const uint32_t (&b
 template <typename TIn> __device__ __forceinline__ uint2 pack(const uint32_t (&b)[2]) {
   if constexpr (sizeof(TIn) == 4) return make_uint2(b[0], b[1]);
   else return make_uint2(b[0] << 16, b[1] << 16);
-}
-
-// View aggregation, fast form for the staged path.  sum / max / conf are the reference's
-// sequential f32 op order (bit-exact); softmax is max-first with exp2 and one reciprocal.
-template <int AGG, int NV>
-__device__ __forceinline__ float aggregate_fast(const float (&s)[NV], int N, const float* __restrict__ cf, int cstride) {
-  if constexpr (AGG != MVN_AGG_SOFTMAX) {
-    return aggregate<AGG, NV>(s, N, cf, cstride);
-  } else {
-    constexpr float kLog2e = 1.4426950408889634f;
-    float m = s[0];
-#pragma unroll
-    for (int v = 1; v < NV; ++v) if (v < N) m = fmaxf(m, s[v]);
-    const float ml = m * kLog2e;
-    float den = 0.f, num = 0.f;
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-      if (v < N) {
-        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[v], kLog2e, -ml));
-        den += e;
-        num = __builtin_fmaf(s[v], e, num);
-      }
-    return num * __builtin_amdgcn_rcpf(den);
-  }
 }
 
 // The LDS region (view) a staged slot index falls in, for one pass.  A select chain over
@@ -341,7 +314,7 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
     if (out_cl) {
       float r[G];
 #pragma unroll
-      for (int ch = 0; ch < G; ++ch) r[ch] = aggregate_fast<AGG, NV>(sv[ch], N, cfb ? cfb + c0 + ch : nullptr, C);
+      for (int ch = 0; ch < G; ++ch) r[ch] = aggregate<AGG, NV>(sv[ch], N, cfb ? cfb + c0 + ch : nullptr, C);
       const uint32_t soff = uint32_t(c0) * uint32_t(sizeof(TOut));
       if constexpr (G == 2) {
         if constexpr (sizeof(TOut) == 4)
@@ -370,7 +343,7 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
       const int c = c0 + ch;
       if (c >= C) break;
       const uint32_t soff = uint32_t(c) * uint32_t(nvox) * uint32_t(sizeof(TOut));
-      buf_store<TOut>(aggregate_fast<AGG, NV>(sv[ch], N, cfb ? cfb + c : nullptr, C), ors, ooff, soff);
+      buf_store<TOut>(aggregate<AGG, NV>(sv[ch], N, cfb ? cfb + c : nullptr, C), ors, ooff, soff);
     }
   };
 
@@ -466,53 +439,37 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
 }  // namespace
 
 template <int AGG, typename TIn, typename TOut>
-int launch_tiled(const void* feat, const float* P, const float* coords, const float* cub, int transfer,
-                 const float* conf, void* out, int B, int N, int C, int H, int W, int Vx, int Vy, int Vz,
-                 int align_corners, int out_cl, int fast, hipStream_t s) {
-  if (out_cl && C % 4 != 0) return MVN_ERR_SHAPE;
+int launch_tiled(const UnprojCall& c) {
+  if (c.out_cl && c.C % 4 != 0) return MVN_ERR_SHAPE;
   if (!unproject_force_generic()) {
     // (fast = MVN_PRECISION_FAST is a property of the chunk-staged kernel; where it does not
     // apply the exact kernel below runs, which is inside the fast mode's tolerance)
-    const int r = launch_x4<AGG, TIn, TOut>(feat, P, coords, cub, transfer, conf, out, B, N, C, H, W, Vx, Vy, Vz,
-                                            align_corners, out_cl, fast, s);
+    const int r = launch_x4<AGG, TIn, TOut>(c);
     if (r != 1) return r;
   }
-  // 32-bit buffer offsets: a frame's maps and volume must stay below 2 GiB
-  if ((long long)N * C * H * W * sizeof(TIn) >= (1LL << 31) ||
-      (long long)C * Vx * Vy * Vz * sizeof(TOut) >= (1LL << 31))
-    return MVN_ERR_SHAPE;
-  // LDS slot budget per pass (clamped in-kernel to the buffer); tests lower it through
-  // mvn_debug_set_unproject to force the multi-pass and global-gather paths.
-  const int knob = unproject_lds_slot_budget();
-  const int budget = knob > 0 ? knob : 1 << 30;
+  if (!frame_fits_32bit<TIn, TOut>(c)) return MVN_ERR_SHAPE;
+  const int budget = lds_slot_budget();
   auto go = [&](auto nv, auto exact) {
     constexpr int NV = decltype(nv)::value;
     using S = TileShape<NV>;
-    const long long nb = (long long)B * ((Vx + S::TX - 1) / S::TX) * ((Vy + S::TY - 1) / S::TY) *
-                         ((Vz + S::TZ - 1) / S::TZ);
-    if (nb > INT_MAX) return false;
-    unproject_tiled<AGG, TIn, TOut, NV, decltype(exact)::value><<<int(nb), S::THREADS, 0, s>>>(
-        static_cast<const TIn*>(feat), P, coords, cub, transfer, conf, static_cast<TOut*>(out), B, N, C, H, W,
-        Vx, Vy, Vz, align_corners, budget, out_cl);
-    return true;
+    const long long nb = tile_blocks(c.B, c.Vx, c.Vy, c.Vz, S::TX, S::TY, S::TZ);
+    if (nb > INT_MAX) return MVN_ERR_SHAPE;
+    unproject_tiled<AGG, TIn, TOut, NV, decltype(exact)::value><<<int(nb), S::THREADS, 0, c.s>>>(
+        static_cast<const TIn*>(c.feat), c.P, c.coords, c.cub, c.transfer, c.conf, static_cast<TOut*>(c.out), c.B,
+        c.N, c.C, c.H, c.W, c.Vx, c.Vy, c.Vz, c.align_corners, budget, c.out_cl);
+    return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
   };
   using I4 = std::integral_constant<int, 4>;
   using I8 = std::integral_constant<int, 8>;
   using T_ = std::true_type;
   using F_ = std::false_type;
-  const bool ok = N == 4 ? go(I4{}, T_{}) : N < 4 ? go(I4{}, F_{}) : N == 8 ? go(I8{}, T_{}) : go(I8{}, F_{});
-  if (!ok) return MVN_ERR_SHAPE;
-  return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
+  return c.N == 4 ? go(I4{}, T_{}) : c.N < 4 ? go(I4{}, F_{}) : c.N == 8 ? go(I8{}, T_{}) : go(I8{}, F_{});
 }
 
-#define MVN_INSTANTIATE(AGG)                                                                                   \
-  template int launch_tiled<AGG, float, float>(const void*, const float*, const float*, const float*, int, const float*, void*,    \
-                                               int, int, int, int, int, int, int, int, int, int, int, hipStream_t);  \
-  template int launch_tiled<AGG, uint16_t, uint16_t>(const void*, const float*, const float*, const float*, int, const float*,     \
-                                                     void*, int, int, int, int, int, int, int, int, int, int,   \
-                                                     int, hipStream_t);                                              \
-  template int launch_tiled<AGG, uint16_t, float>(const void*, const float*, const float*, const float*, int, const float*, void*, \
-                                                  int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
+#define MVN_INSTANTIATE(AGG)                                             \
+  template int launch_tiled<AGG, float, float>(const UnprojCall&);       \
+  template int launch_tiled<AGG, uint16_t, uint16_t>(const UnprojCall&); \
+  template int launch_tiled<AGG, uint16_t, float>(const UnprojCall&);
 MVN_INSTANTIATE(MVN_AGG_SUM)
 MVN_INSTANTIATE(MVN_AGG_MAX)
 MVN_INSTANTIATE(MVN_AGG_SOFTMAX)

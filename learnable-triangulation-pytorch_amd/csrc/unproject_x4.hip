@@ -73,15 +73,8 @@ template <> struct X4Shape<4> {
   static constexpr int NV = 4, G = 4, TX = 8, TY = 8, TZ = 8, THREADS = 512, SLOTS = 1536, MC = 1, WAVES = 6;
   static constexpr int STORE_F32 = kStorePolicyF32;
 };
-#ifndef MVN_FAST_BF16_SHAPE
-#define MVN_FAST_BF16_SHAPE 4
-#endif
 
-// LDS slot: one pixel's G channels as f32
-template <int G> struct SlotT;
-template <> struct SlotT<4> { using type = uint4; };
-template <> struct SlotT<2> { using type = uint2; };
-// channel pair q of a slot
+// channel pair q of a slot (SlotT<G>: one pixel's G channels as f32)
 __device__ __forceinline__ f2 slot_pair(const uint4& s, int q) { return q ? hi2(s) : lo2(s); }
 __device__ __forceinline__ f2 slot_pair(const uint2& s, int) { return f2{__uint_as_float(s.x), __uint_as_float(s.y)}; }
 
@@ -113,9 +106,9 @@ template <int NV> struct RegionSet {
                        int((c >> 13) & 0x7ffu), int(c >> 24));
   }
   __device__ __forceinline__ Region get(int v) const { return unpack(a[v], b[v], c[v]); }
-  // u per lane: plain selects (9 v_cndmask).  Not through readfirstlane as pick_region does:
-  // a convergent op cannot be speculated, so each select became a branch tree with exec
-  // masking (~4,200 cycles of block prologue at config 2, profiles/r13_x4_stamps.txt).
+  // u per lane: plain selects (9 v_cndmask).  Not through readfirstlane: a convergent op
+  // cannot be speculated, so each select became a branch tree with exec masking (~4,200
+  // cycles of block prologue at config 2, profiles/r13_x4_stamps.txt).
   __device__ __forceinline__ Region pick(int u) const {
     uint32_t pa = a[0], pb = b[0], pc = c[0];
 #pragma unroll
@@ -744,52 +737,36 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
 // Returns MVN_OK, an error code, or 1 when this kernel does not apply (the caller then
 // runs unproject_tiled).
 template <int AGG, typename TIn, typename TOut>
-int launch_x4(const void* feat, const float* P, const float* coords, const float* cub, int transfer,
-              const float* conf, void* out, int B, int N, int C, int H, int W, int Vx, int Vy, int Vz,
-              int align_corners, int out_cl, int fast, hipStream_t s) {
-  if (H > 32000 || W > 32000 || W % 4 != 0) return 1;
+int launch_x4(const UnprojCall& c) {
+  if (c.H > 32000 || c.W > 32000 || c.W % 4 != 0) return 1;
   // 4 views: tile per input dtype (A/B at the bench configs), f32 4x8x16,
-  // bf16 4x8x8; 8 views: 2-channel slots, NCDHW output only
-  const bool four = N == 4 && C % 4 == 0, eight = N == 8 && C % 2 == 0 && !out_cl;
+  // bf16 8x8x8; 8 views: 2-channel slots, NCDHW output only
+  const bool four = c.N == 4 && c.C % 4 == 0, eight = c.N == 8 && c.C % 2 == 0 && !c.out_cl;
   if (!four && !eight) return 1;
-  if ((long long)N * C * H * W * sizeof(TIn) >= (1LL << 31) ||
-      (long long)C * Vx * Vy * Vz * sizeof(TOut) >= (1LL << 31))
-    return MVN_ERR_SHAPE;
-  const int knob = unproject_lds_slot_budget();
-  const int budget = knob > 0 ? knob : 1 << 30;
-  auto go = [&](auto shape, auto cl) {
-    constexpr int K = decltype(shape)::value, CL = decltype(cl)::value;
+  if (!frame_fits_32bit<TIn, TOut>(c)) return MVN_ERR_SHAPE;
+  const int budget = lds_slot_budget();
+  auto launch = [&](auto shape, auto cl, auto fast) {
+    constexpr int K = decltype(shape)::value, CL = decltype(cl)::value, FAST = decltype(fast)::value;
     using S = X4Shape<K>;
-    const long long nb = (long long)B * ((Vx + S::TX - 1) / S::TX) * ((Vy + S::TY - 1) / S::TY) *
-                         ((Vz + S::TZ - 1) / S::TZ);
+    const long long nb = tile_blocks(c.B, c.Vx, c.Vy, c.Vz, S::TX, S::TY, S::TZ);
     if (nb > INT_MAX) return MVN_ERR_SHAPE;
-    if constexpr (K == 2 && CL == 0 && MVN_FAST_BF16_SHAPE == 4) {
-      if (fast) {       // bf16 maps, NCDHW, fast arithmetic: the 8x8x8 tile (X4Shape<4>)
-        using S4 = X4Shape<4>;
-        const long long nb4 = (long long)B * ((Vx + S4::TX - 1) / S4::TX) * ((Vy + S4::TY - 1) / S4::TY) *
-                              ((Vz + S4::TZ - 1) / S4::TZ);
-        if (nb4 > INT_MAX) return MVN_ERR_SHAPE;
-        unproject_x4<AGG, TIn, TOut, 4, 0, 1><<<int(nb4), S4::THREADS, 0, s>>>(
-            static_cast<const TIn*>(feat), P, coords, cub, transfer, conf, static_cast<TOut*>(out), B, C, H, W, Vx,
-            Vy, Vz, align_corners, budget);
-        return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
-      }
-    }
-    if (fast)
-      unproject_x4<AGG, TIn, TOut, K, CL, 1><<<int(nb), S::THREADS, 0, s>>>(
-          static_cast<const TIn*>(feat), P, coords, cub, transfer, conf, static_cast<TOut*>(out), B, C, H, W, Vx, Vy,
-          Vz, align_corners, budget);
-    else
-      unproject_x4<AGG, TIn, TOut, K, CL, 0><<<int(nb), S::THREADS, 0, s>>>(
-          static_cast<const TIn*>(feat), P, coords, cub, transfer, conf, static_cast<TOut*>(out), B, C, H, W, Vx, Vy,
-          Vz, align_corners, budget);
+    unproject_x4<AGG, TIn, TOut, K, CL, FAST><<<int(nb), S::THREADS, 0, c.s>>>(
+        static_cast<const TIn*>(c.feat), c.P, c.coords, c.cub, c.transfer, c.conf, static_cast<TOut*>(c.out), c.B,
+        c.C, c.H, c.W, c.Vx, c.Vy, c.Vz, c.align_corners, budget);
     return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
   };
-  using NC = std::integral_constant<int, 0>;
-  using CLv = std::integral_constant<int, 1>;
-  if (eight) return go(std::integral_constant<int, 3>{}, NC{});
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  auto go = [&](auto shape, auto cl) {
+    constexpr int K = decltype(shape)::value, CL = decltype(cl)::value;
+    // bf16 maps, NCDHW, fast arithmetic: the 8x8x8 tile at 6 waves per SIMD (X4Shape<4>)
+    if constexpr (K == 2 && CL == 0)
+      if (c.fast) return launch(std::integral_constant<int, 4>{}, cl, I1{});
+    return c.fast ? launch(shape, cl, I1{}) : launch(shape, cl, I0{});
+  };
+  if (eight) return go(std::integral_constant<int, 3>{}, I0{});
   using K4 = std::integral_constant<int, sizeof(TIn) == 2 ? 2 : 0>;
-  return out_cl ? go(K4{}, CLv{}) : go(K4{}, NC{});
+  return c.out_cl ? go(K4{}, I1{}) : go(K4{}, I0{});
 }
 
 // Diagnostics (mvn_debug_unproject_occupancy): resident blocks per CU of the softmax kernels.
@@ -803,16 +780,10 @@ int x4_blocks_per_cu(int bf16) {
   return e == hipSuccess ? n : MVN_ERR_LAUNCH;
 }
 
-#define MVN_INSTANTIATE(AGG)                                                                                   \
-  template int launch_x4<AGG, float, float>(const void*, const float*, const float*, const float*, int,        \
-                                            const float*, void*, int, int, int, int, int, int, int, int, int,  \
-                                            int, int, hipStream_t);                                            \
-  template int launch_x4<AGG, uint16_t, uint16_t>(const void*, const float*, const float*, const float*, int,  \
-                                                  const float*, void*, int, int, int, int, int, int, int, int, \
-                                                  int, int, int, hipStream_t);                                      \
-  template int launch_x4<AGG, uint16_t, float>(const void*, const float*, const float*, const float*, int,     \
-                                               const float*, void*, int, int, int, int, int, int, int, int,    \
-                                               int, int, int, hipStream_t);
+#define MVN_INSTANTIATE(AGG)                                          \
+  template int launch_x4<AGG, float, float>(const UnprojCall&);       \
+  template int launch_x4<AGG, uint16_t, uint16_t>(const UnprojCall&); \
+  template int launch_x4<AGG, uint16_t, float>(const UnprojCall&);
 MVN_INSTANTIATE(MVN_AGG_SUM)
 MVN_INSTANTIATE(MVN_AGG_MAX)
 MVN_INSTANTIATE(MVN_AGG_SOFTMAX)

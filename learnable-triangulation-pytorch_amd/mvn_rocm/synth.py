@@ -14,6 +14,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from .volumetric import rotation_matrix  # noqa: F401  (also used as synth.rotation_matrix by the golden script)
+
 IMAGE_SIZE = 384          # experiments/human36m/train/human36m_vol_softmax.yaml:6
 HEATMAP_SIZE = 96         # PoseResNet output stride 4 (pose_resnet.py:205-226)
 CUBOID_SIDE = 2500.0      # human36m_vol_softmax.yaml: cuboid_side
@@ -77,18 +79,6 @@ def projections(cams, image_size=IMAGE_SIZE, heatmap_size=HEATMAP_SIZE) -> np.nd
         c2.update_after_resize((image_size, image_size), (heatmap_size, heatmap_size))
         out.append(c2.projection)
     return np.stack(out)
-
-
-def rotation_matrix(axis, theta: float) -> np.ndarray:
-    """Counter-clockwise rotation about `axis` (quaternion form of volumetric.py:87-99)."""
-    axis = np.asarray(axis, dtype=np.float64)
-    axis = axis / math.sqrt(float(axis @ axis))
-    a = math.cos(theta / 2.0)
-    b, c, d = -axis * math.sin(theta / 2.0)
-    return np.array([
-        [a * a + b * b - c * c - d * d, 2 * (b * c + a * d), 2 * (b * d - a * c)],
-        [2 * (b * c - a * d), a * a + c * c - b * b - d * d, 2 * (c * d + a * b)],
-        [2 * (b * d + a * c), 2 * (c * d - a * b), a * a + d * d - b * b - c * c]])
 
 
 def coord_volume(base_point: np.ndarray, theta: float, volume_size: int = VOLUME_SIZE,
