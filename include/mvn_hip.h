@@ -25,6 +25,9 @@
  *   mvn_triangulate_ransac <- mvn/models/triangulation.py:54-128 (the RANSAC baseline's host
  *                           loop: hypotheses, inlier DLT, Huber refinement)
  *   mvn_reprojection_error <- mvn/utils/multiview.py:177-184 calc_reprojection_error_matrix(...)
+ *   mvn_algebraic_triangulate <- mvn/models/triangulation.py:164-191 (AlgebraicTriangulationNet's
+ *                           forward after the backbone: mvn_softargmax2d, the confidence
+ *                           normalisation, the upscale and mvn_dlt in one launch)
  *
  * Conventions
  *   - Every buffer is caller-owned device memory (hipMalloc / torch), contiguous,
@@ -381,6 +384,35 @@ int mvn_triangulate_ransac(const float* proj, const float* pts, const int32_t* p
                            int pairs_per_point, int n_iters, float epsilon, int direct_optimization,
                            float* out_xyz, uint32_t* out_inliers, float* out_error_mean,
                            int B, int N, int J, void* stream);
+
+/*
+ * The algebraic model's forward after the backbone in one launch.  Replaces the chain of
+ * mvn/models/triangulation.py:164-191: 2D soft-argmax of heatmaps * multiplier per view
+ * (mvn_softargmax2d's arithmetic: the same bits), confidence normalisation
+ * c / sum_v c + 1e-5 (f32, the sum sequential in view order; :173-174), upscale to image
+ * pixels (:182-183) and the confidence-weighted DLT (mvn_dlt's arithmetic: the same bits as
+ * mvn_dlt on out_kp2d and out_conf).
+ *
+ *   heatmaps  (B, N, J, H, W)  dtype (f32 | bf16), contiguous
+ *   proj      (B, N, 3, 4) f32  image-resolution projection matrices
+ *   conf      (B, N, J)    f32  raw per-view confidences; NULL = all ones (:161)
+ *   scale_x, scale_y            image width / W, image height / H
+ *   out_xyz   (B, J, 3)    f32
+ *   out_kp2d  (B, N, J, 2) f32  2D points in image pixels: out_xy * (scale_x, scale_y)
+ *   out_xy    (B, N, J, 2) f32  2D points in heatmap pixels (what a backward needs)
+ *   out_conf  (B, N, J)    f32  normalised confidences
+ *   out_maps  (B, N, J, H, W) maps_dtype: the maps mvn_softargmax2d returns; NULL = not wanted
+ *
+ * One block per (b, j): meant for small batches (latency), 1 <= N <= 32.  Stream-ordered,
+ * reentrant, no workspace.  MVN_ERR_ARG for a null required pointer or softmax not 0 / 1;
+ * MVN_ERR_SHAPE for N > 32 or a non-positive or too large extent; MVN_ERR_DTYPE for a
+ * (dtype, maps_dtype) other than f32/f32, bf16/bf16, bf16/f32.  Checked before any HIP call.
+ */
+int mvn_algebraic_triangulate(const void* heatmaps, int dtype, float multiplier, int softmax,
+                              const float* proj, const float* conf, float scale_x, float scale_y,
+                              float* out_xyz, float* out_kp2d, float* out_xy, float* out_conf,
+                              void* out_maps, int maps_dtype,
+                              int B, int N, int J, int H, int W, void* stream);
 
 /*
  * Test hook (tests only; process-wide, thread-safe): force unprojection code paths.

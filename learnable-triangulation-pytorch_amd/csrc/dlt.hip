@@ -29,70 +29,12 @@ __global__ __launch_bounds__(kDltBlock) void dlt_kernel(const float* __restrict_
   if (t >= B * J) return;
   const int b = t / J, j = t - b * J;
 
-  double R[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) R[i][k] = 0.0;
-
-  for (int v = 0; v < N; ++v) {
-    const float* Pv = P + (size_t(b) * N + v) * 12;
-    const size_t pj = (size_t(b) * N + v) * J + j;
-    const float pt[2] = {pts[pj * 2 + 0], pts[pj * 2 + 1]};
-    const float cf = conf ? conf[pj] : 1.f;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      double a[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float e = Pv[8 + k] * pt[r];   // multiview.py:150
-        e = e - Pv[r * 4 + k];         // multiview.py:151
-        e = e * cf;                    // multiview.py:152
-        a[k] = double(e);
-      }
-      givens_fold(R, a);
-    }
-  }
-
-  // An exactly zero column k of A (all-zero confidences, a coordinate no camera sees) leaves
-  // R's column k exactly zero (the rotations mix rows, never columns), and e_k is an exact null
-  // vector; LAPACK's SVD returns it as V[:, 3], the last of the tied smallest singular values
-  // when there are several (A = 0: V = I, so e_4 and the point (0, 0, 0)).  The reference's
-  // X[:3] / X[3] then gives (0, 0, 0) for k = 3 and (nan, nan, +-inf) otherwise
-  // (multiview.py:154-157); iterating on the singular R would return ratios of tiny numbers.
-  int zcol = -1;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    bool z = true;
-#pragma unroll
-    for (int i = 0; i <= k; ++i) z &= R[i][k] == 0.0;
-    if (z) zcol = k;
-  }
-  double X[4];
-  if (zcol >= 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) X[i] = i == zcol ? 1.0 : 0.0;
-  } else if (!inverse_iteration(R, X)) {
-    double V[4][4];
-    jacobi_svd(R, V);
-    int kmin = 0;
-    double smin = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const double n2 = R[0][k] * R[0][k] + R[1][k] * R[1][k] + R[2][k] * R[2][k] + R[3][k] * R[3][k];
-      if (k == 0 || n2 <= smin) { smin = n2; kmin = k; }     // ties: the last, as LAPACK's order
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      X[i] = V[i][0];
-#pragma unroll
-      for (int k = 1; k < 4; ++k) if (kmin == k) X[i] = V[i][k];
-    }
-  }
+  float x[3];
+  dlt_point(P, pts, conf, b, j, N, J, x);
   float* o = out + size_t(t) * 3;
-  o[0] = float(X[0] / X[3]);
-  o[1] = float(X[1] / X[3]);
-  o[2] = float(X[2] / X[3]);
+  o[0] = x[0];
+  o[1] = x[1];
+  o[2] = x[2];
 }
 
 }  // namespace

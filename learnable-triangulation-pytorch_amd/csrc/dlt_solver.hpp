@@ -151,5 +151,80 @@ __device__ __forceinline__ bool inverse_iteration(const double (&R)[4][4], doubl
   return false;
 }
 
+// One confidence-weighted DLT point (multiview.py:132-159), point (b, j) of P (B, N, 3, 4),
+// pts (B, N, J, 2) and conf (B, N, J) or null (all ones).  Shared by dlt_kernel (dlt.hip: one
+// lane per point, inputs in global memory) and algebraic_kernel (algebraic.hip: one point's
+// pts and conf in LDS, as a (1, N, 1) batch), so both return the same bits.
+//   1. rows of A in f32 exactly as multiview.py:150-152 forms them (A = P[2]*pt; A -= P[:2];
+//      A *= conf — three separately rounded ops), folded into R by Givens rotations (f64),
+//   2. the null vector: exact zero column, inverse iteration, or the Jacobi SVD,
+//   3. X[:3] / X[3] (multiview.py:157; the sign of the null vector cancels).
+__device__ __forceinline__ void dlt_point(const float* P, const float* pts, const float* conf, int b, int j, int N,
+                                          int J, float (&o)[3]) {
+  double R[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) R[i][k] = 0.0;
+
+  for (int v = 0; v < N; ++v) {
+    const float* Pv = P + (size_t(b) * N + v) * 12;
+    const size_t pj = (size_t(b) * N + v) * J + j;
+    const float pt[2] = {pts[pj * 2 + 0], pts[pj * 2 + 1]};
+    const float cf = conf ? conf[pj] : 1.f;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      double a[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float e = Pv[8 + k] * pt[r];   // multiview.py:150
+        e = e - Pv[r * 4 + k];         // multiview.py:151
+        e = e * cf;                    // multiview.py:152
+        a[k] = double(e);
+      }
+      givens_fold(R, a);
+    }
+  }
+
+  // An exactly zero column k of A (all-zero confidences, a coordinate no camera sees) leaves
+  // R's column k exactly zero (the rotations mix rows, never columns), and e_k is an exact null
+  // vector; LAPACK's SVD returns it as V[:, 3], the last of the tied smallest singular values
+  // when there are several (A = 0: V = I, so e_4 and the point (0, 0, 0)).  The reference's
+  // X[:3] / X[3] then gives (0, 0, 0) for k = 3 and (nan, nan, +-inf) otherwise
+  // (multiview.py:154-157); iterating on the singular R would return ratios of tiny numbers.
+  int zcol = -1;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    bool z = true;
+#pragma unroll
+    for (int i = 0; i <= k; ++i) z &= R[i][k] == 0.0;
+    if (z) zcol = k;
+  }
+  double X[4];
+  if (zcol >= 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) X[i] = i == zcol ? 1.0 : 0.0;
+  } else if (!inverse_iteration(R, X)) {
+    double V[4][4];
+    jacobi_svd(R, V);
+    int kmin = 0;
+    double smin = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double n2 = R[0][k] * R[0][k] + R[1][k] * R[1][k] + R[2][k] * R[2][k] + R[3][k] * R[3][k];
+      if (k == 0 || n2 <= smin) { smin = n2; kmin = k; }     // ties: the last, as LAPACK's order
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      X[i] = V[i][0];
+#pragma unroll
+      for (int k = 1; k < 4; ++k) if (kmin == k) X[i] = V[i][k];
+    }
+  }
+  o[0] = float(X[0] / X[3]);
+  o[1] = float(X[1] / X[3]);
+  o[2] = float(X[2] / X[3]);
+}
+
 }  // namespace
 }  // namespace mvn

@@ -72,6 +72,8 @@ SIGNATURES = {
     "mvn_reprojection_error": (_c_int, [_c_void_p] * 4 + [_c_int, _c_int, _c_int, _c_void_p]),
     "mvn_triangulate_ransac": (_c_int, [_c_void_p] * 3 + [_c_int, _c_int, _c_float, _c_int] + [_c_void_p] * 3
                                + [_c_int, _c_int, _c_int, _c_void_p]),
+    "mvn_algebraic_triangulate": (_c_int, [_c_void_p, _c_int, _c_float, _c_int, _c_void_p, _c_void_p, _c_float,
+                                           _c_float] + [_c_void_p] * 5 + [_c_int] + [_c_int] * 5 + [_c_void_p]),
     "mvn_debug_set_unproject": (_c_int, [_c_int, _c_int]),
     "mvn_debug_device_asserts": (_c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint),
                                           ctypes.POINTER(ctypes.c_uint)]),

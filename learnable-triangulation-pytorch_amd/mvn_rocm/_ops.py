@@ -252,6 +252,47 @@ def _(proj, pts, conf):
     return pts.new_empty((B, J, 3), dtype=torch.float32)
 
 
+# --------------------------------------------------------------------------- algebraic model, one launch
+ALGEBRAIC_MAX_VIEWS = 32      # csrc/algebraic.hip: LDS holds the views' points and confidences
+
+
+@_op("algebraic_triangulate")
+def algebraic_triangulate(hm: Tensor, proj: Tensor, conf: Optional[Tensor], softmax: bool, multiplier: float,
+                          scale_x: float, scale_y: float, return_maps: bool,
+                          out_dtype: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """hm (B,N,J,H,W) f32|bf16 contiguous, proj (B,N,3,4) f32, conf (B,N,J) f32 raw or None (ones)
+    -> (xyz (B,J,3), kp2d (B,N,J,2) image px, xy (B,N,J,2) heatmap px, normalised conf (B,N,J),
+    all f32, maps (B,N,J,H,W) or an empty tensor).  N <= ALGEBRAIC_MAX_VIEWS."""
+    _require_gpu(hm, proj, conf)
+    B, N, J, H, W = hm.shape
+    dev = hm.device
+    xyz = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+    kp2d = torch.empty((B, N, J, 2), dtype=torch.float32, device=dev)
+    xy = torch.empty((B, N, J, 2), dtype=torch.float32, device=dev)
+    cn = torch.empty((B, N, J), dtype=torch.float32, device=dev)
+    if return_maps:
+        maps = torch.empty((B, N, J, H, W), dtype=_CODE_DTYPE[out_dtype], device=dev)
+    else:
+        maps = torch.empty((0,), dtype=_CODE_DTYPE[out_dtype], device=dev)
+    if xyz.numel() == 0:
+        return xyz, kp2d, xy, cn, maps
+    code = _lib.load().mvn_algebraic_triangulate(
+        hm.data_ptr(), _DTYPE_CODE[hm.dtype], float(multiplier), int(softmax), proj.data_ptr(), _ptr(conf),
+        float(scale_x), float(scale_y), xyz.data_ptr(), kp2d.data_ptr(), xy.data_ptr(), cn.data_ptr(),
+        maps.data_ptr() if return_maps else None, out_dtype, B, N, J, H, W, _stream(hm))
+    _lib.check(code, "mvn_algebraic_triangulate")
+    return xyz, kp2d, xy, cn, maps
+
+
+@algebraic_triangulate.register_fake
+def _(hm, proj, conf, softmax, multiplier, scale_x, scale_y, return_maps, out_dtype):
+    B, N, J = hm.shape[:3]
+    f32 = dict(dtype=torch.float32)
+    shape = tuple(hm.shape) if return_maps else (0,)
+    return (hm.new_empty((B, J, 3), **f32), hm.new_empty((B, N, J, 2), **f32), hm.new_empty((B, N, J, 2), **f32),
+            hm.new_empty((B, N, J), **f32), hm.new_empty(shape, dtype=_CODE_DTYPE[out_dtype]))
+
+
 # --------------------------------------------------------------------------- RANSAC
 @_op("reprojection_error")
 def reprojection_error(points3d: Tensor, pts: Tensor, proj: Tensor) -> Tensor:

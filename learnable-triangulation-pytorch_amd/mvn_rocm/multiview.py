@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib
 from . import _ops
 
 
@@ -161,3 +162,148 @@ def triangulate_ransac(proj_matricies, points, n_iters=10, reprojection_error_ep
                                             n_iters=n_iters, reprojection_error_epsilon=reprojection_error_epsilon,
                                             direct_optimization=direct_optimization, generator=generator)
     return xyz[0, 0], torch.nonzero(inliers[0, 0]).flatten()
+
+
+# ------------------------------------------------------------------------------- algebraic model
+# Largest B * J that `fused=None` still sends to the one-launch kernel (csrc/algebraic.hip: one
+# block per (b, j), whose one-wave DLT tail keeps the next block off its CU).  The derivable
+# rule is one block per CU of the MI355X (256); measured (profiles/time_algebraic.txt, N = 4,
+# J = 17, 96^2): faster than the composition by more than the spread up to B = 16 (272 points:
+# 50 vs 62 us), slower from B = 64 (1088 points: 126 vs 63 us) — 272 is the largest measured
+# size at which the kernel is not slower.
+FUSED_MAX_POINTS = 272
+
+
+def _compose_from_heatmaps(hm, proj, conf, softmax, multiplier, scale_x, scale_y, return_heatmaps, out_dtype):
+    """triangulation.py:164-191 from the separate ops (differentiable through their own
+    autograd functions)."""
+    from . import op
+    B, N, J, H, W = hm.shape
+    xy, maps = op.integrate_tensor_2d(hm.reshape(B * N, J, H, W), softmax, multiplier=multiplier,
+                                      return_heatmaps=return_heatmaps, out_dtype=out_dtype)
+    xy = xy.view(B, N, J, 2)
+    if conf is None:                                                # triangulation.py:161
+        conf = torch.ones((B, N, J), dtype=torch.float32, device=hm.device)
+    conf = conf / conf.sum(dim=1, keepdim=True) + 1e-5              # triangulation.py:173-174
+    kp2d = torch.stack([xy[..., 0] * scale_x, xy[..., 1] * scale_y], dim=-1)   # triangulation.py:181-183
+    xyz = triangulate_batch_of_points(proj, kp2d, conf)
+    return xyz, kp2d, (maps.view(B, N, J, H, W) if return_heatmaps else None), conf
+
+
+def triangulate_from_heatmaps(heatmaps, proj_matricies, confidences=None, *, image_shape, heatmap_multiplier=1.0,
+                              heatmap_softmax=True, return_heatmaps=True, out_dtype=None, fused=None):
+    """The algebraic model's forward after the backbone, in one call.
+
+    Reference: ``AlgebraicTriangulationNet.forward``, ``mvn/models/triangulation.py:164-191``.
+      heatmaps (B, N, J, H, W) — or (B*N, J, H, W), as the backbone returns them, the views then
+      taken from proj_matricies — float32 or bfloat16, before the multiplier and the softmax;
+      proj_matricies (B, N, 3, 4); confidences (B, N, J) or (B*N, J), raw (``alg_confidences``
+      of the backbone), or None for the model without confidences (all ones, ``:161``);
+      image_shape (height, width) of the images the projections refer to (``:177``).
+    Returns ``forward``'s tuple: keypoints_3d (B, J, 3), keypoints_2d (B, N, J, 2) in image
+    pixels, the normalised heatmaps (B, N, J, H, W) in ``out_dtype`` (default: the input's) or
+    None with ``return_heatmaps=False``, and the normalised confidences (B, N, J).
+
+    ``fused``: True — one launch (csrc/algebraic.hip); False — the composition of
+    ``integrate_tensor_2d``, the normalisation and ``triangulate_batch_of_points``; None
+    (default) — the fused kernel up to ``FUSED_MAX_POINTS`` points (B * J), the composition
+    above.  Both compute the same 2D points, maps and — given the same confidences — joints bit
+    for bit; the fused confidences are summed in view order (torch's sum for N <= 4).  More
+    than 32 views always take the composition.  Differentiable with respect to the heatmaps
+    and the confidences on both paths.
+    """
+    from . import op
+    hm = heatmaps
+    if proj_matricies.dim() != 4 or proj_matricies.shape[2:] != (3, 4):
+        raise RuntimeError(f"proj_matricies must be (B, N, 3, 4), got {tuple(proj_matricies.shape)}")
+    B, N = proj_matricies.shape[:2]
+    if hm.dim() == 4:
+        if hm.shape[0] != B * N:
+            raise AssertionError("heatmaps and proj_matricies must have the same number of views")
+        hm = hm.reshape(B, N, *hm.shape[1:])
+    if hm.dim() != 5:
+        raise RuntimeError(f"heatmaps must be (B, N, J, H, W) or (B*N, J, H, W), got {tuple(heatmaps.shape)}")
+    if hm.shape[:2] != (B, N):                                      # multiview.py:143
+        raise AssertionError("heatmaps and proj_matricies must have the same number of views")
+    J, H, W = hm.shape[2:]
+    in_code = op._dtype_code(hm.dtype)                              # TypeError for anything else
+    od = op._dtype_code(out_dtype if out_dtype is not None else hm.dtype)
+    if (in_code, od) == (_lib.MVN_DTYPE_F32, _lib.MVN_DTYPE_BF16):
+        raise TypeError("float32 heatmaps cannot return bfloat16 maps (bfloat16 in, float32 or bfloat16 out)")
+    conf = confidences
+    if conf is not None:
+        if conf.dim() == 2 and conf.shape[0] == B * N:
+            conf = conf.reshape(B, N, conf.shape[1])
+        if conf.shape[:2] != (B, N):
+            raise AssertionError("confidences and proj_matricies must have the same number of views")
+        if tuple(conf.shape) != (B, N, J):
+            raise RuntimeError(f"confidences must be {(B, N, J)}, got {tuple(conf.shape)}")
+        conf = _ops.f32c(conf)
+    hm = hm.contiguous()
+    proj = _ops.f32c(proj_matricies)
+    scale_x, scale_y = image_shape[1] / W, image_shape[0] / H      # triangulation.py:182-183
+    out_t = _ops._CODE_DTYPE[od]
+    use_fused = (B * J <= FUSED_MAX_POINTS) if fused is None else bool(fused)
+    if not use_fused or N > _ops.ALGEBRAIC_MAX_VIEWS:
+        return _compose_from_heatmaps(hm, proj, conf, bool(heatmap_softmax), float(heatmap_multiplier), scale_x,
+                                      scale_y, bool(return_heatmaps), out_t)
+    args = (hm, proj, conf, bool(heatmap_softmax), float(heatmap_multiplier), float(scale_x), float(scale_y),
+            bool(return_heatmaps), od)
+    if op._needs_grad(hm, conf):
+        xyz, kp2d, maps, cn = AlgebraicFunction.apply(*args)
+    else:
+        xyz, kp2d, _, cn, maps = _ops.call(_ops.algebraic_triangulate, *args)
+    return xyz, kp2d, (maps if return_heatmaps else None), cn
+
+
+class _Saved:
+    """What the existing backward functions read from an autograd context."""
+
+    def __init__(self, saved_tensors, cfg=None, needs_input_grad=()):
+        self.saved_tensors, self.cfg, self.needs_input_grad = saved_tensors, cfg, needs_input_grad
+
+
+class AlgebraicFunction(torch.autograd.Function):
+    """autograd surface of triangulate_from_heatmaps' fused path.  No backward kernel of its own:
+    the DLT backward (csrc/backward.hip) on the saved image-pixel points and normalised
+    confidences, the normalisation's Jacobian and the scale as tensor algebra, and the 2D
+    soft-argmax backward on the saved heatmaps and heatmap-pixel points."""
+
+    @staticmethod
+    def forward(ctx, hm, proj, conf, softmax, multiplier, scale_x, scale_y, return_maps, out_dtype):
+        xyz, kp2d, xy, cn, maps = _ops.call(_ops.algebraic_triangulate, hm, proj, conf, softmax, multiplier,
+                                            scale_x, scale_y, return_maps, out_dtype)
+        ctx.save_for_backward(hm, proj, conf, xy, kp2d, cn)
+        ctx.cfg = (softmax, multiplier, scale_x, scale_y)
+        ctx.set_materialize_grads(False)
+        return xyz, kp2d, maps, cn
+
+    @staticmethod
+    def backward(ctx, g_xyz, g_kp2d, g_maps, g_cn):
+        from . import _backward
+        hm, proj, conf, xy, kp2d, cn = ctx.saved_tensors
+        softmax, multiplier, scale_x, scale_y = ctx.cfg
+        want_hm, want_conf = ctx.needs_input_grad[0], conf is not None and ctx.needs_input_grad[2]
+        B, N, J, H, W = hm.shape
+        # keypoints_3d -> (keypoints_2d, normalised confidences)
+        if g_xyz is not None:
+            _, g_pts, g_c = _backward.dlt_backward(_Saved((proj, kp2d, cn), needs_input_grad=(False, True, True)), g_xyz)
+            g_kp2d = g_pts if g_kp2d is None else g_kp2d + g_pts
+            g_cn = g_c if g_cn is None else g_cn + g_c
+        g_conf = None
+        if want_conf and g_cn is not None:
+            # c_u = r_u / s + 1e-5, s = sum_v r_v:  dL/dr_v = g_v / s - sum_u g_u r_u / s^2
+            s = conf.sum(dim=1, keepdim=True)
+            g_conf = g_cn / s - (g_cn * conf).sum(dim=1, keepdim=True) / (s * s)
+        g_hm = None
+        if want_hm:
+            g_xy = None
+            if g_kp2d is not None:
+                g_xy = (g_kp2d * g_kp2d.new_tensor([scale_x, scale_y])).reshape(B * N, J, 2)
+            gm = g_maps.reshape(B * N, J, H, W) if (g_maps is not None and g_maps.numel() > 0) else None
+            if g_xy is None and gm is None:
+                g_hm = torch.zeros_like(hm)
+            else:
+                saved = _Saved((hm.view(B * N, J, H, W), xy.view(B * N, J, 2)), cfg=(softmax, multiplier))
+                g_hm = _backward.softargmax2d_backward(saved, g_xy, gm)[0].view_as(hm)
+        return g_hm, None, g_conf, None, None, None, None, None, None
