@@ -164,14 +164,20 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
   __shared__ Slot stageB[kBuf];
   __shared__ int red[kWaves][NV][4];
 
-  // ---- which tile (z-tiles fastest; block order as unproject_tiled) ------------------
+  // ---- which tile (z-tiles fastest; unproject_tiled's block order, the slab rotated by frame) ---
   const int nTx = (Vx + TX - 1) / TX, nTy = (Vy + TY - 1) / TY, nTz = (Vz + TZ - 1) / TZ;
   int L = int(blockIdx.x);
   {
     const int nf = nTx * nTy * nTz;
     if (nf % 8 == 0) {
       const int xcd = int(blockIdx.x) % 8, k = int(blockIdx.x) / 8, slab = nf / 8;
-      L = (k / slab) * nf + xcd * slab + k % slab;
+      // Blocks go to the 8 XCDs round-robin, so XCD j works on one x-slab of every frame, and
+      // the staged footprint differs between the slabs (mean chunks per tile at the bench
+      // geometry: 285 346 373 381 379 359 314 227, tools/footprints.py), for every frame
+      // alike.  XCD j takes slab (j + frame) % 8: over 8 frames every XCD sees every slab
+      // position, while all XCDs still work on one frame at a time.
+      const int frame = k / slab;
+      L = frame * nf + ((xcd + frame) % 8) * slab + k % slab;
     }
   }
   const int tz = L % nTz; L /= nTz;

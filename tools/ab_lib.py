@@ -2,6 +2,9 @@
 in one process, interleaved rounds; outputs are checked bitwise against the first build.
 
     python tools/ab_lib.py path/to/libA.so path/to/libB.so ...
+
+AB_ROUNDS (default 3) sets the number of interleaved rounds; AB_CFG4=1 adds the 8-view config, AB_ONLY=cfgN
+keeps one.  The same library twice (a byte copy) gives the spread of the protocol.
 """
 import ctypes
 import os
@@ -48,7 +51,7 @@ def main():
                                   code, B, NV, 32, 96, 96, 64, 64, 64, agg, 0, stream)
             assert r == 0, r
 
-        for rnd in range(3):
+        for rnd in range(int(os.environ.get("AB_ROUNDS", "3"))):      # the minimum over the rounds is reported
             for name, lib in libs:
                 for agg, aname in ((2, "softmax"), (0, "sum")):
                     out = outs.setdefault((name, aname), torch.empty((B, 32, 64, 64, 64), dtype=dt, device=dev))
