@@ -447,6 +447,23 @@ int mvn_debug_dassert_selftest(int n, void* stream);
  */
 int mvn_debug_unproject_occupancy(int bf16_maps);
 
+/*
+ * Diagnostics, host only (no device needed): the block -> tile order of the four-view
+ * unprojection kernel (csrc/x4_order.hpp).  tiles[i] receives the tile that block i of a launch
+ * over `frames` frames of nTx x nTy x nTz tiles works on (frame-major, then x, y, z tiles, z
+ * fastest).  order: 0..3 = an X4Order of x4_order.hpp, -1 = the one the kernel is built with.
+ * Returns MVN_OK, or MVN_ERR_ARG (null pointer, a count < 1, more than INT_MAX blocks, unknown
+ * order).
+ */
+int mvn_debug_x4_block_tiles(int order, int frames, int nTx, int nTy, int nTz, int* tiles);
+
+/*
+ * Diagnostics, host only: image slots (pixels) one LDS pass of the four-view kernel holds, for
+ * its f32 (shape 0), bf16 (1) or 8-view (2) tile shape; a tile whose footprints sum to more is
+ * staged in several passes.  Returns the count, or MVN_ERR_ARG for an unknown shape.
+ */
+int mvn_debug_x4_image_slots(int shape);
+
 #ifdef __cplusplus
 }
 #endif

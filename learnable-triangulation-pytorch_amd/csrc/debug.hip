@@ -3,6 +3,7 @@
 #include <atomic>
 
 #include "unproject_common.hpp"
+#include "x4_order.hpp"
 
 namespace mvn {
 
@@ -26,6 +27,19 @@ bool unproject_force_generic() { return g_force_simple.load(std::memory_order_re
 
 extern "C" int mvn_debug_unproject_occupancy(int bf16_maps) {
   return mvn::unproj::x4_blocks_per_cu(bf16_maps ? 1 : 0);
+}
+
+extern "C" int mvn_debug_x4_image_slots(int shape) {
+  return shape < 0 || shape > 2 ? MVN_ERR_ARG : mvn::unproj::x4_image_slots(shape);
+}
+
+extern "C" int mvn_debug_x4_block_tiles(int order, int frames, int nTx, int nTy, int nTz, int* tiles) {
+  const long long nb = (long long)frames * nTx * nTy * nTz;
+  if (!tiles || frames < 1 || nTx < 1 || nTy < 1 || nTz < 1 || nb > INT_MAX) return MVN_ERR_ARG;
+  if (order < -1 || order > mvn::unproj::kX4OrderCentre3D) return MVN_ERR_ARG;
+  const int use = order < 0 ? mvn::unproj::x4_launch_order() : order;
+  for (int i = 0; i < int(nb); ++i) tiles[i] = mvn::unproj::x4_block_tile(i, nTx, nTy, nTz, use);
+  return MVN_OK;
 }
 
 extern "C" int mvn_debug_dassert_selftest(int n, void* stream) {

@@ -510,6 +510,10 @@ template <int AGG, typename TIn, typename TOut> int launch_tiled(const UnprojCal
 template <int AGG, typename TIn, typename TOut> int launch_x4(const UnprojCall& c);
 // Diagnostics (mvn_debug_unproject_occupancy): resident blocks per CU of the softmax kernels.
 int x4_blocks_per_cu(int bf16);
+// ... (mvn_debug_x4_block_tiles / mvn_debug_x4_image_slots): the X4Order the four-view kernel is
+// built with, and the image slots of one LDS pass of its f32 (0), bf16 (1) or 8-view (2) shape.
+int x4_launch_order();
+int x4_image_slots(int shape);
 
 }  // namespace unproj
 }  // namespace mvn

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "unproject_common.hpp"
+#include "x4_order.hpp"
 
 namespace mvn {
 namespace unproj {
@@ -39,9 +40,19 @@ namespace {
 // NV views, G channels per LDS slot (16-byte slots of 4 f32 channels, or 8-byte slots of 2),
 // MC chunk slots per thread, WAVES waves per SIMD the register allocation must allow.
 template <int K> struct X4Shape;
+// Block -> tile order (x4_order.hpp).  The paired and centre-first orders, which the schedule
+// model (tools/schedule_model.py) puts 4-6 % ahead, measured 0.2-1.4 % slower than the
+// rotated slabs at config 2, 2-4 % at config 3 and 9-20 % at config 4 (profiles/r23_ab_variants.txt).
+constexpr int kX4Order = kX4OrderSlab;
+// 4 views, f32 maps.  2,432 slots: two buffers and the box reductions are 78,336 bytes, the most
+// that keeps 2 blocks per CU in the 160 KB of LDS (the register budget of 4 waves per SIMD allows
+// no third).  A pass then holds 2,366 image slots and every tile of the bench geometry (largest
+// footprint 2,156) takes the pipelined one-pass path; at 2,048 slots 43 of a launch's 4,096 tiles
+// took the multi-pass path, all of a frame's on one XCD: config 2 142.0 -> 136.9 us (r23).  The
+// regions' packing holds: sbase < 2,366 < 2^13, cbase <= kCap = 1,024 < 2^11.
 // STORE_F32: cache policy of f32 output stores (non-temporal for 64-byte z-runs).
-template <> struct X4Shape<0> {   // 4 views, f32 maps
-  static constexpr int NV = 4, G = 4, TX = 4, TY = 8, TZ = 16, THREADS = 512, SLOTS = 2048, MC = 2, WAVES = 4;
+template <> struct X4Shape<0> {
+  static constexpr int NV = 4, G = 4, TX = 4, TY = 8, TZ = 16, THREADS = 512, SLOTS = 2432, MC = 2, WAVES = 4;
   static constexpr int STORE_F32 = kStorePolicyF32;
 };
 // 4 views, bf16 maps (widened exactly to f32 slots when staged): an 8x8x8 tile of 512 threads,
@@ -154,6 +165,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
   // per buffer: image slots [0, kTrash), 64 per-lane trash slots (the masked-off pixels of
   // a chunk are written there: no exec-mask branch per write), 2 zero slots
   constexpr int kZeroSlot = kBuf - 2, kTrash = kBuf - 2 - kWave;
+  static_assert(kBuf <= (1 << 13) && kCap < (1 << 11), "RegionSet packs sbase in 13 bits and cbase in 11");
   // LDS slot = one pixel's G channels as f32 (16 / 8 bytes; bf16 maps are widened exactly
   // when staged: bf16 slots halve the LDS bytes but the per-tap widening costs more VALU, r13)
   using Slot = typename SlotT<G>::type;
@@ -164,22 +176,9 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
   __shared__ Slot stageB[kBuf];
   __shared__ int red[kWaves][NV][4];
 
-  // ---- which tile (z-tiles fastest; unproject_tiled's block order, the slab rotated by frame) ---
+  // ---- which tile (z-tiles fastest; the block order of x4_order.hpp) ----------------------
   const int nTx = (Vx + TX - 1) / TX, nTy = (Vy + TY - 1) / TY, nTz = (Vz + TZ - 1) / TZ;
-  int L = int(blockIdx.x);
-  {
-    const int nf = nTx * nTy * nTz;
-    if (nf % 8 == 0) {
-      const int xcd = int(blockIdx.x) % 8, k = int(blockIdx.x) / 8, slab = nf / 8;
-      // Blocks go to the 8 XCDs round-robin, so XCD j works on one x-slab of every frame, and
-      // the staged footprint differs between the slabs (mean chunks per tile at the bench
-      // geometry: 285 346 373 381 379 359 314 227, tools/footprints.py), for every frame
-      // alike.  XCD j takes slab (j + frame) % 8: over 8 frames every XCD sees every slab
-      // position, while all XCDs still work on one frame at a time.
-      const int frame = k / slab;
-      L = frame * nf + ((xcd + frame) % 8) * slab + k % slab;
-    }
-  }
+  int L = x4_block_tile(int(blockIdx.x), nTx, nTy, nTz, kX4Order);
   const int tz = L % nTz; L /= nTz;
   const int ty = L % nTy; L /= nTy;
   const int tx = L % nTx;
@@ -786,7 +785,14 @@ int x4_blocks_per_cu(int bf16) {
   return e == hipSuccess ? n : MVN_ERR_LAUNCH;
 }
 
-#define MVN_INSTANTIATE(AGG)                                          \
+int x4_launch_order() { return kX4Order; }
+// kTrash of the kernel: a buffer's slots less the 64 trash and 2 zero slots
+int x4_image_slots(int shape) {
+  const int slots = shape == 0 ? X4Shape<0>::SLOTS : shape == 1 ? X4Shape<2>::SLOTS : X4Shape<3>::SLOTS;
+  return slots - 2 - kWave;
+}
+
+#define MVN_INSTANTIATE(AGG)                                         \
   template int launch_x4<AGG, float, float>(const UnprojCall&);       \
   template int launch_x4<AGG, uint16_t, uint16_t>(const UnprojCall&); \
   template int launch_x4<AGG, uint16_t, float>(const UnprojCall&);

@@ -79,6 +79,8 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_uint)]),
     "mvn_debug_dassert_selftest": (_c_int, [_c_int, _c_void_p]),
     "mvn_debug_unproject_occupancy": (_c_int, [_c_int]),
+    "mvn_debug_x4_block_tiles": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_int)]),
+    "mvn_debug_x4_image_slots": (_c_int, [_c_int]),
 }
 
 _lib = None
