@@ -119,6 +119,11 @@ int mvn_unproject(const void* feat, int feat_dtype,
  *             write the normalised volume
  *   softmax   1 = softmax over the flattened volume (op.py:89),
  *             0 = relu with no mass normalisation (op.py:91, reference quirk)
+ *   NaN       follows torch in both modes.  softmax: a joint holding a NaN (or +inf) voxel is
+ *             NaN in coordinates and volume.  relu keeps a NaN as F.relu does (relu(NaN) = NaN,
+ *             not 0): the voxel is NaN in out_vol and the joint's coordinates are NaN; a +inf
+ *             voxel stays +inf.  Other joints are untouched.  mvn_softargmax3d_backward masks
+ *             like torch's relu backward (x <= 0), so a NaN voxel receives its gradient.
  *   workspace >= mvn_softargmax3d_workspace_bytes(B, J, Vx, Vy, Vz) bytes of
  *             device memory, 16-byte aligned; contents need no initialisation.
  */
@@ -221,6 +226,9 @@ int mvn_unproject_v2v_front_ex(const void* feat, int feat_dtype, const float* pr
  *   out_xy    (B, J, 2)     f32: (x, y) = sum p * (w, h) / sum p  (op.py:31-42)
  *   out_maps  (B, J, H, W)  out_dtype: softmax-normalised (softmax = 1) or relu'd maps
  *                           (softmax = 0, not normalised, op.py:27); NULL = not wanted
+ * NaN follows torch in both modes: a map holding a NaN pixel has NaN (x, y); softmax makes the
+ * whole returned map NaN, relu keeps the NaN at its pixel (F.relu(NaN) = NaN, not 0).  The same
+ * holds for the maps and 2D points of mvn_algebraic_triangulate.
  */
 int mvn_softargmax2d(const void* heatmaps, int dtype, float multiplier, int softmax, float* out_xy,
                      void* out_maps, int out_dtype, int B, int J, int H, int W, void* stream);

@@ -19,7 +19,7 @@ constexpr int kBwdPartial = 3;      // m, S = sum e, T = sum e * d
 // p = softmax(mult * x) (or relu(mult * x)), xyz = sum_i p_i c_i.  With upstream gradients
 // gx (B,J,3) and gv (B,J,V):   d_i = gv_i + gx . c_i
 //   softmax:  dL/dx_i = mult * p_i * (d_i - sum_k p_k d_k)
-//   relu:     dL/dx_i = mult * [mult * x_i > 0] * d_i
+//   relu:     dL/dx_i = mult * [not (mult * x_i <= 0)] * d_i   (a NaN x_i passes, as torch's)
 // Pass 1 (softmax only) reduces, per (b, j, chunk), the local max m, S = sum e^(mx-m) and
 // T = sum e^(mx-m) d with one wave per chunk; pass 2 folds them (r = T / S, M, S) and
 // writes dL/dx elementwise.
@@ -109,7 +109,8 @@ __global__ __launch_bounds__(kThreads) void sa_bwd_apply(const TV* __restrict__ 
       const float p = __expf(x - M) * invS;
       g = mult * p * (d - r);
     } else {
-      g = x > 0.f ? mult * d : 0.f;
+      // torch's threshold_backward masks with x <= 0: a NaN input passes the gradient
+      g = x <= 0.f ? 0.f : mult * d;
     }
     store_elem(oj + i, g);
   }

@@ -32,6 +32,11 @@ template <typename T> __device__ __forceinline__ void store_elem(T* p, float v);
 template <> __device__ __forceinline__ void store_elem<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void store_elem<uint16_t>(uint16_t* p, float v) { *p = f32_to_bf16(v); }
 
+// relu as torch computes it (op.py:27, :91): a NaN stays NaN — fmaxf(v, 0.f) returns the 0 for
+// a quiet NaN, which hid a NaN voxel or pixel in relu mode while softmax mode propagated it
+// (tests/test_gpu_softargmax_paths.py::test_nonfinite_voxels_follow_torch).
+__device__ __forceinline__ float relu_keep_nan(float v) { return (v <= 0.f) ? 0.f : v; }
+
 // ---- wave reductions (64 lanes) -----------------------------------------
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

@@ -273,7 +273,7 @@ __global__ __launch_bounds__(kSaBlock) void softargmax_partials(
       for (int r = 0; r < RUNS; ++r)
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-          const float e = fmaxf(x[r][k] * mult, 0.f);
+          const float e = relu_keep_nan(x[r][k] * mult);
           s += e;
           sx = __builtin_fmaf(e, c[r][3 * k], sx);
           sy = __builtin_fmaf(e, c[r][3 * k + 1], sy);
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(kSaBlock) void softargmax_finalize(
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       const float v = t[r][k] * mult;
-      y[k] = SOFTMAX ? __expf(v - m) * inv : fmaxf(v, 0.f);
+      y[k] = SOFTMAX ? __expf(v - m) * inv : relu_keep_nan(v);
     }
     if constexpr (sizeof(TO) == sizeof(T)) {
       store_run<TO, VEC, kFinalNtStores>(oj, i, nvox, vec_ok, y);

@@ -63,7 +63,7 @@ __device__ __forceinline__ void softargmax2d_map(const T* hm, float mult, TO* ou
   float s = 0.f, sx = 0.f, sy = 0.f;
   for (int i = t; i < n; i += kBlock) {
     const float v = to_f32(p[i]) * mult;
-    const float e = SOFTMAX ? __expf(v - M) : fmaxf(v, 0.f);
+    const float e = SOFTMAX ? __expf(v - M) : relu_keep_nan(v);
     const int h = i / W, w = i - h * W;
     s += e;
     sx = __builtin_fmaf(e, float(w), sx);
@@ -83,7 +83,7 @@ __device__ __forceinline__ void softargmax2d_map(const T* hm, float mult, TO* ou
     TO* o = out + map * size_t(n);
     for (int i = t; i < n; i += kBlock) {
       const float v = to_f32(p[i]) * mult;
-      store_elem(o + i, SOFTMAX ? __expf(v - M) * inv : fmaxf(v, 0.f));
+      store_elem(o + i, SOFTMAX ? __expf(v - M) * inv : relu_keep_nan(v));
     }
   }
 }
@@ -153,7 +153,7 @@ __device__ __forceinline__ void softargmax2d_map_reg(const T* hm, float mult, TO
     const int h = i / W, w0 = i - h * W;      // a run of 4 stays in one row (W % 4 == 0)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float e = SOFTMAX ? __expf(v[r][k] - M) : fmaxf(v[r][k], 0.f);
+      const float e = SOFTMAX ? __expf(v[r][k] - M) : relu_keep_nan(v[r][k]);
       v[r][k] = e;
       s += e;
       sx = __builtin_fmaf(e, float(w0 + k), sx);

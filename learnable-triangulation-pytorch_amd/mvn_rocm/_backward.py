@@ -151,7 +151,8 @@ def softargmax2d_backward(ctx, grad_xy, grad_maps):
     96, 96)-small; no kernel of its own).  With v = multiplier * h, e = exp(v - max) or
     relu(v), S = sum e, p = e / S, (X, Y) = sum p * (w, h):
       softmax: dL/dv = p * ((w - X) gX + (h - Y) gY + g_map - sum(g_map * p))
-      relu:    dL/dv = [v > 0] * (((w - X) gX + (h - Y) gY) / S + g_map)
+      relu:    dL/dv = [not (v <= 0)] * (((w - X) gX + (h - Y) gY) / S + g_map)
+    (torch's relu backward masks with v <= 0, so a NaN v passes its gradient)
     """
     hm, xy = ctx.saved_tensors
     softmax, mult = ctx.cfg
@@ -179,5 +180,5 @@ def softargmax2d_backward(ctx, grad_xy, grad_maps):
         g = geo / S
         if has_gm:
             g = g + grad_maps.float()
-        gv = g * (v > 0).to(g.dtype)
+        gv = g * (~(v <= 0)).to(g.dtype)
     return (gv * mult).to(hm.dtype), None, None, None, None

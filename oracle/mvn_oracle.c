@@ -153,7 +153,9 @@ int oracle_softargmax3d(const float *vol, const float *coords, float multiplier,
             }
             for (long i = 0; i < nvox; ++i) {
                 double x = (double)(vj[i] * multiplier);
-                double p = softmax ? exp(x - m) / den : (x > 0.0 ? x : 0.0);
+                /* relu as torch's (op.py:91): a NaN stays NaN.  (softmax: the maximum above skips
+                 * a NaN, but exp(NaN - m) makes den, hence the whole joint, NaN as torch does.) */
+                double p = softmax ? exp(x - m) / den : (x <= 0.0 ? 0.0 : x);
                 if (oj) oj[i] = (float)p;
                 ax += p * cb[i * 3 + 0];
                 ay += p * cb[i * 3 + 1];

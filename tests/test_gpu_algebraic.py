@@ -178,6 +178,42 @@ def test_nan_pixel_stays_in_its_joint(device, H, W):
     assert not np.isnan(cn).any()
 
 
+@pytest.mark.parametrize("H,W", [(16, 16), (17, 23)], ids=["register", "three_pass"])
+def test_relu_nan_pixel_follows_torch(device, H, W):
+    """relu mode (heatmap_softmax=False): torch's relu keeps a NaN (op.py:27), so the map's
+    (x, y) are NaN and the returned map holds the NaN at its pixel — op.integrate_tensor_2d on
+    both map bodies against torch on the CPU (float64 on the float32 products), then the fused
+    call against the composed ops."""
+    from mvn_rocm import multiview, op
+    from oracle import restate_torch
+    B, N, J = 2, 3, 5
+    hm, proj, conf = _heatmaps(B, N, J, H, W, torch.float32, device), _proj(B, N, J, device), _conf(B, N, J, device)
+    hm[1, 2, 4, H // 2, 3] = float("nan")
+    bad = np.zeros((B * N, J), bool)
+    bad[1 * N + 2, 4] = True
+    xy, maps = op.integrate_tensor_2d(hm.view(B * N, J, H, W), False, multiplier=MULT)
+    scaled = (hm.cpu().view(B * N, J, H, W) * torch.tensor(MULT, dtype=torch.float32)).double()
+    rxy, rmaps = restate_torch.integrate_tensor_2d(scaled, False)
+    xy, maps, rxy, rmaps = _f32(xy), _f32(maps), rxy.numpy(), rmaps.numpy()
+    assert (np.isnan(rxy).all(axis=-1) == bad).all() and (np.isnan(rxy).any(axis=-1) == bad).all()
+    assert (np.isnan(xy) == np.isnan(rxy)).all()
+    assert max_rel(xy[~bad], rxy[~bad]) <= 1e-5
+    assert np.isnan(rmaps).sum() == 1 and (np.isnan(maps) == np.isnan(rmaps)).all()
+    assert_bits_equal(np.nan_to_num(maps, nan=0.0), np.nan_to_num(rmaps, nan=0.0).astype(np.float32))
+    kw = dict(image_shape=(64, 64), heatmap_multiplier=MULT, heatmap_softmax=False)
+    fused = multiview.triangulate_from_heatmaps(hm, proj, conf, fused=True, **kw)
+    composed = multiview.triangulate_from_heatmaps(hm, proj, conf, fused=False, **kw)
+    for a, b in zip(fused, composed):
+        _assert_same_with_nans(a, b)
+    xyz, kp2d, fmaps, cn = (_f32(t) for t in fused)
+    nan_x = np.zeros((B, J), bool)
+    nan_x[1, 4] = True
+    assert (np.isnan(xyz).any(axis=-1) == nan_x).all()
+    assert (np.isnan(kp2d).any(axis=-1).reshape(B * N, J) == bad).all()
+    assert (np.isnan(fmaps).reshape(B * N, J, -1).sum(-1) == bad).all()
+    assert not np.isnan(cn).any()
+
+
 def test_more_views_than_the_kernel_takes(device):
     """N = 33: Python routes around the kernel (MVN_ERR_SHAPE in the C ABI), whatever `fused`."""
     from mvn_rocm import multiview

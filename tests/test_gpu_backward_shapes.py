@@ -360,6 +360,34 @@ def test_softargmax_neg_inf_logits_follow_torch(device, dt, softmax):
     _same_nonfinite(grad, rgrad)
 
 
+def test_softargmax_relu_nan_voxel_follows_torch(device):
+    """relu mode, one NaN voxel in joint 1: torch's relu keeps the NaN (the joint's coordinates
+    are NaN, the returned volume holds it at that voxel) and its backward masks with x <= 0, so
+    the NaN voxel receives mult * d like a positive one and every gradient stays finite."""
+    from mvn_rocm import op, synth
+    g = torch.Generator().manual_seed(45)
+    coords = synth.volumetric_batch(1, channels=1, volume=16, seed=4).coords
+    vol = 3.0 * torch.randn((1, 3, 4096), generator=g)
+    vol[0, 1, 1500] = float("nan")
+    gx = 1e-3 * torch.randn((1, 3, 3), generator=g)
+    gv = 0.1 * torch.randn((1, 3, 16, 16, 16), generator=g)
+    mult = 1.7
+    v = vol.view(1, 3, 16, 16, 16).to(device).requires_grad_(True)
+    xyz, vols = op.integrate_tensor_3d_with_coordinates(v, coords.to(device), False, multiplier=mult)
+    torch.autograd.backward([xyz, vols], [gx.to(device), gv.to(device)])
+    xyz, vols, grad = xyz.detach().cpu().numpy(), vols.detach().cpu().numpy(), v.grad.cpu().numpy()
+    rxyz, rvols, rgrad = cases.softargmax_ref_explicit(vol.view(1, 3, 16, 16, 16), coords, False, mult, gx, gv)
+    assert np.isnan(rxyz[0, 1]).all() and np.isfinite(rxyz[0, (0, 2), :]).all()
+    assert np.isnan(rvols).sum() == 1 and np.isfinite(rgrad).all()
+    assert rgrad.reshape(1, 3, -1)[0, 1, 1500] != 0
+    _same_nonfinite(xyz, rxyz)
+    _same_nonfinite(vols, rvols)
+    _same_nonfinite(grad, rgrad)
+    per_joint = max_rel_per(grad, rgrad, 2)
+    print(f"relu, NaN voxel: per joint {per_joint.max():.2e}")
+    assert per_joint.max() <= 1e-4, per_joint
+
+
 # ---------------------------------------------------------------- 5. DLT: several blocks
 def _joints_first(a):
     return np.moveaxis(a, 2, 1)          # (B, N, J, ..) -> (B, J, N, ..)

@@ -90,6 +90,35 @@ def test_softargmax_oracles(golden, softmax, mult):
     np.testing.assert_array_equal(tvol.numpy(), d[f"vol_{key}"])
 
 
+@pytest.mark.parametrize("softmax", (True, False))
+@pytest.mark.parametrize("mult", (1.0, 1.7))
+def test_softargmax_oracle_nonfinite_voxels_follow_torch(golden, softmax, mult):
+    """One NaN voxel in joint 1 and one +inf voxel in joint 2 of frame 0: the C oracle has NaN
+    and infinities exactly where torch's softmax / relu and einsum (op.py:89-94) put them —
+    relu keeps a NaN (F.relu(nan) = nan), so joint 1's coordinates are NaN in both modes — and
+    the bars of test_softargmax_oracles on the rest."""
+    d = golden("softargmax_small.npz")
+    vol = d["vol"].copy()
+    B, J = vol.shape[:2]
+    assert J >= 3
+    flat = vol.reshape(B, J, -1)
+    flat[0, 1, flat.shape[2] // 3] = np.nan
+    flat[0, 2, flat.shape[2] // 2] = np.inf
+    xyz, out = capi.softargmax3d(vol, d["coords"], softmax, mult)
+    txyz, tout = restate_torch.integrate_tensor_3d_with_coordinates(torch.from_numpy(vol) * mult,
+                                                                    torch.from_numpy(d["coords"]), softmax)
+    txyz, tout = txyz.numpy(), tout.numpy()
+    assert np.isnan(txyz[0, 1]).all() and not np.isfinite(txyz[0, 2]).any()
+    assert np.isnan(tout[0, 1]).sum() == (tout[0, 1].size if softmax else 1)
+    for ours, ref, tol in ((xyz, txyz, 5e-6), (out, tout, 1e-6)):
+        assert (np.isnan(ours) == np.isnan(ref)).all()
+        inf = np.isinf(ref)
+        assert (np.isinf(ours) == inf).all() and (ours[inf] == ref[inf]).all()
+        fin = np.isfinite(ref)
+        assert fin.any()
+        assert max_rel(ours[fin], ref[fin]) <= tol
+
+
 def test_softargmax_oracle_blob(golden):
     d = golden("softargmax_blob.npz")
     xyz, vol = capi.softargmax3d(d["vol"], d["coords"], True, 1.0)
