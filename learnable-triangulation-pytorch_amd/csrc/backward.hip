@@ -6,6 +6,7 @@
 // The reference gets these from ATen autograd (softmax / einsum / torch.svd backward); here
 // they are closed forms evaluated in one or two streaming passes.
 #include "common.hpp"
+#include "wave_reduce.hpp"
 
 namespace mvn {
 namespace {
@@ -26,14 +27,22 @@ constexpr int kBwdPartial = 3;      // m, S = sum e, T = sum e * d
 
 template <typename T> __device__ __forceinline__ float ld(const T* p, long long i) { return to_f32(p[i]); }
 
-__device__ __forceinline__ void merge3(float& m, float& s, float& t, float m2, float s2, float t2) {
-  const float M = fmaxf(m, m2);
-  const float ka = (m == -INFINITY) ? 0.f : __expf(m - M);
-  const float kb = (m2 == -INFINITY) ? 0.f : __expf(m2 - M);
-  s = s * ka + s2 * kb;
-  t = t * ka + t2 * kb;
-  m = M;
-}
+// The upstream gradient of one (b, j): d(i) = gv_i + gx . c_i, either part optional.
+template <typename TG>
+struct Upstream {
+  const TG* gv;          // (nvox) of this (b, j), or null
+  const float* cb;       // the frame's coordinates
+  float g0, g1, g2;
+  __device__ __forceinline__ Upstream(const float* gxyz, const TG* gvol, const float* coords, int b, int j, int J,
+                                      int nvox)
+      : gv(gvol ? gvol + (size_t(b) * J + j) * nvox : nullptr), cb(coords + size_t(b) * nvox * 3),
+        g0(0.f), g1(0.f), g2(0.f) {
+    if (gxyz) { const float* g = gxyz + (size_t(b) * J + j) * 3; g0 = g[0]; g1 = g[1]; g2 = g[2]; }
+  }
+  __device__ __forceinline__ float d(int i) const {
+    return (gv ? ld(gv, i) : 0.f) + g0 * cb[size_t(i) * 3] + g1 * cb[size_t(i) * 3 + 1] + g2 * cb[size_t(i) * 3 + 2];
+  }
+};
 
 template <typename TV, typename TG>
 __global__ __launch_bounds__(kThreads) void sa_bwd_partials(const TV* __restrict__ vol, long long bs, long long js,
@@ -45,32 +54,25 @@ __global__ __launch_bounds__(kThreads) void sa_bwd_partials(const TV* __restrict
   const int j = blockIdx.y * (kThreads / kWave) + threadIdx.x / kWave;
   if (j >= J) return;                                   // no barriers in this kernel
   const TV* vj = vol + b * bs + j * js;
-  const TG* gj = gvol ? gvol + (size_t(b) * J + j) * nvox : nullptr;
-  const float* cb = coords + size_t(b) * nvox * 3;
-  float g0 = 0.f, g1 = 0.f, g2 = 0.f;
-  if (gxyz) { const float* g = gxyz + (size_t(b) * J + j) * 3; g0 = g[0]; g1 = g[1]; g2 = g[2]; }
-  float m = -INFINITY, s = 0.f, t = 0.f;
+  const Upstream<TG> up(gxyz, gvol, coords, b, j, J, nvox);
+  float m = -INFINITY, st[2] = {0.f, 0.f};              // S, T
   for (int i = chunk * kChunk + lane; i < min(nvox, (chunk + 1) * kChunk); i += kWave) {
     const float x = ld(vj, i) * mult;
-    const float d = (gj ? ld(gj, i) : 0.f) + g0 * cb[size_t(i) * 3] + g1 * cb[size_t(i) * 3 + 1] + g2 * cb[size_t(i) * 3 + 2];
+    const float d = up.d(i);
     if (x > m) {
       const float k = (m == -INFINITY) ? 0.f : __expf(m - x);
-      s *= k; t *= k; m = x;
+      st[0] *= k; st[1] *= k; m = x;
     }
     // a -inf logit has p = 0 (torch: gradient exactly 0 there) and leaves the running maximum
     // alone: with m still -inf, x - m would be -inf - -inf = NaN (the forward guards it too)
     const float e = (x == -INFINITY) ? 0.f : __expf(x - m);
-    s += e;
-    t = __builtin_fmaf(e, d, t);
+    st[0] += e;
+    st[1] = __builtin_fmaf(e, d, st[1]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, kWave), s2 = __shfl_xor(s, o, kWave), t2 = __shfl_xor(t, o, kWave);
-    merge3(m, s, t, m2, s2, t2);
-  }
+  wave_softmax_merge<true>(m, st);
   if (lane == 0) {
     float* o = part + ((size_t(b) * J + j) * npart + chunk) * kBwdPartial;
-    o[0] = m; o[1] = s; o[2] = t;
+    o[0] = m; o[1] = st[0]; o[2] = st[1];
   }
 }
 
@@ -85,25 +87,18 @@ __global__ __launch_bounds__(kThreads) void sa_bwd_apply(const TV* __restrict__ 
   float M = 0.f, S = 1.f, r = 0.f;
   if constexpr (SOFTMAX) {
     const float* pj = part + (size_t(b) * J + j) * npart * kBwdPartial;
-    float m = -INFINITY, s = 0.f, t = 0.f;
-    for (int k = lane; k < npart; k += kWave) merge3(m, s, t, pj[k * 3], pj[k * 3 + 1], pj[k * 3 + 2]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float m2 = __shfl_xor(m, o, kWave), s2 = __shfl_xor(s, o, kWave), t2 = __shfl_xor(t, o, kWave);
-      merge3(m, s, t, m2, s2, t2);
-    }
-    M = m; S = s; r = t / s;
+    float m = -INFINITY, st[2] = {0.f, 0.f};
+    for (int k = lane; k < npart; k += kWave) softmax_merge<true>(m, st, pj[k * 3], {pj[k * 3 + 1], pj[k * 3 + 2]});
+    wave_softmax_merge<true>(m, st);
+    M = m; S = st[0]; r = st[1] / st[0];
   }
   const TV* vj = vol + b * bs + j * js;
-  const TG* gj = gvol ? gvol + (size_t(b) * J + j) * nvox : nullptr;
-  const float* cb = coords + size_t(b) * nvox * 3;
-  float g0 = 0.f, g1 = 0.f, g2 = 0.f;
-  if (gxyz) { const float* g = gxyz + (size_t(b) * J + j) * 3; g0 = g[0]; g1 = g[1]; g2 = g[2]; }
+  const Upstream<TG> up(gxyz, gvol, coords, b, j, J, nvox);
   const float invS = 1.f / S;
   TO* oj = gin + (size_t(b) * J + j) * nvox;
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < nvox; i += gridDim.x * kThreads) {
     const float x = ld(vj, i) * mult;
-    const float d = (gj ? ld(gj, i) : 0.f) + g0 * cb[size_t(i) * 3] + g1 * cb[size_t(i) * 3 + 1] + g2 * cb[size_t(i) * 3 + 2];
+    const float d = up.d(i);
     float g;
     if constexpr (SOFTMAX) {
       const float p = __expf(x - M) * invS;
@@ -293,14 +288,9 @@ int sa_bwd_launch(const void* vol, long long bs, long long js, const float* coor
     if (!launch_ok()) return MVN_ERR_LAUNCH;
   }
   const int gx = min((nvox + kThreads - 1) / kThreads, 64);
-  if (softmax)
-    sa_bwd_apply<TV, TG, TO, true><<<dim3(gx, J, B), kThreads, 0, st>>>(
-        static_cast<const TV*>(vol), bs, js, coords, mult, gxyz, static_cast<const TG*>(gvol), part,
-        static_cast<TO*>(gin), J, nvox, npart);
-  else
-    sa_bwd_apply<TV, TG, TO, false><<<dim3(gx, J, B), kThreads, 0, st>>>(
-        static_cast<const TV*>(vol), bs, js, coords, mult, gxyz, static_cast<const TG*>(gvol), part,
-        static_cast<TO*>(gin), J, nvox, npart);
+  (softmax ? sa_bwd_apply<TV, TG, TO, true> : sa_bwd_apply<TV, TG, TO, false>)<<<dim3(gx, J, B), kThreads, 0, st>>>(
+      static_cast<const TV*>(vol), bs, js, coords, mult, gxyz, static_cast<const TG*>(gvol), part,
+      static_cast<TO*>(gin), J, nvox, npart);
   return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
 }
 

@@ -11,30 +11,13 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "wave_reduce.hpp"
 
 namespace mvn {
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
-
-template <int CTRL, int RMASK> __device__ __forceinline__ float dpp(float v, float ident) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ident), __float_as_int(v), CTRL, RMASK, 0xf, false));
-}
-// Wave reductions valid in lane 63 (row_shr steps, then row_bcast:15 / row_bcast:31).
-__device__ __forceinline__ float wave_max63(float v) {
-  const float I = -INFINITY;
-  v = fmaxf(v, dpp<0x111, 0xf>(v, I)); v = fmaxf(v, dpp<0x112, 0xf>(v, I));
-  v = fmaxf(v, dpp<0x114, 0xf>(v, I)); v = fmaxf(v, dpp<0x118, 0xf>(v, I));
-  v = fmaxf(v, dpp<0x142, 0xa>(v, I)); v = fmaxf(v, dpp<0x143, 0xc>(v, I));
-  return v;
-}
-__device__ __forceinline__ float wave_sum63(float v) {
-  v += dpp<0x111, 0xf>(v, 0.f); v += dpp<0x112, 0xf>(v, 0.f);
-  v += dpp<0x114, 0xf>(v, 0.f); v += dpp<0x118, 0xf>(v, 0.f);
-  v += dpp<0x142, 0xa>(v, 0.f); v += dpp<0x143, 0xc>(v, 0.f);
-  return v;
-}
 
 // Three passes over map `map` of hm (n = H * W pixels each, any shape and alignment): the max,
 // then (sum e, sum e*w, sum e*h), then the normalised map into out (skipped when out is null).
@@ -115,14 +98,8 @@ __device__ __forceinline__ void softargmax2d_map_reg(const T* hm, float mult, TO
   for (int r = 0; r < kRuns; ++r) {
     const int i = (r * kBlock + t) * 4;
     if (i < n) {
-      if constexpr (sizeof(T) == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p + i);
-        v[r][0] = q.x; v[r][1] = q.y; v[r][2] = q.z; v[r][3] = q.w;
-      } else {
-        const uint2 q = *reinterpret_cast<const uint2*>(p + i);
-        v[r][0] = __uint_as_float(q.x << 16); v[r][1] = __uint_as_float(q.x & 0xffff0000u);
-        v[r][2] = __uint_as_float(q.y << 16); v[r][3] = __uint_as_float(q.y & 0xffff0000u);
-      }
+      if constexpr (sizeof(T) == 4) widen<T>(*reinterpret_cast<const u4v*>(p + i), v[r]);
+      else widen(*reinterpret_cast<const u2v*>(p + i), v[r]);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[r][k] = v[r][k] * mult;
     } else {
