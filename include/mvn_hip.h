@@ -22,7 +22,10 @@
  *                           argmin)
  *   mvn_v2v_front        <- mvn/models/v2v.py:7-17, 145-146 (V2VModel.front_layers[0] =
  *                           Basic3DBlock(32, 16, 7), eval mode; BASELINE config 5)
- *   mvn_triangulate_ransac <- mvn/models/triangulation.py:54-128 (the RANSAC baseline's host
+ *   mvn_v2v_head         <- mvn/models/v2v.py:154-160 (back_layers[1], back_layers[2] and
+ *                           output_layer: the pointwise tail, eval mode), and with the 3D
+ *                           soft-argmax behind it mvn_v2v_head_softargmax
+ *   mvn_triangulate_ransac <-mvn/models/triangulation.py:54-128 (the RANSAC baseline's host
  *                           loop: hypotheses, inlier DLT, Huber refinement)
  *   mvn_reprojection_error <- mvn/utils/multiview.py:177-184 calc_reprojection_error_matrix(...)
  *   mvn_algebraic_triangulate <- mvn/models/triangulation.py:164-191 (AlgebraicTriangulationNet's
@@ -218,6 +221,66 @@ int mvn_unproject_v2v_front_ex(const void* feat, int feat_dtype, const float* pr
                                const float* shift, void* out, int out_dtype, void* workspace,
                                size_t workspace_bytes, int group_frames, int B, int N, int C, int H, int W,
                                int V, void* stream);
+
+/*
+ * V2V head, eval mode: the pointwise tail of V2VModel (v2v.py:154-160) in one kernel on bf16
+ * MFMA with f32 accumulation.  Per voxel, with 32 -> 32 -> 32 -> J channels (1 <= J <= 32):
+ *   h1 = relu(bn1(W1 x + b1))    back_layers[1] = Basic3DBlock(32, 32, 1)
+ *   h2 = relu(bn2(W2 h1 + b2))   back_layers[2] = Basic3DBlock(32, 32, 1)
+ *   y  = W3 h2 + b3              output_layer   = Conv3d(32, J, 1)
+ * x is rounded to bf16 (nearest-even) when it arrives as f32; h = relu(acc * scale + shift) is
+ * formed in f32 (one fma) and rounded to bf16 as the next layer's operand; y = acc + bias3 in
+ * f32.  relu keeps a NaN (as F.relu): a NaN or infinite input voxel makes all J logits of that
+ * voxel NaN or infinite, as torch does, and touches no other voxel.
+ *   x              x_layout MVN_LAYOUT_NCDHW: (B, 32, Vx, Vy, Vz), x_dtype f32 | bf16;
+ *                  MVN_LAYOUT_NDHWC: (B, Vx, Vy, Vz, 32), bf16 only
+ *   weight_packed  mvn_v2v_head_packed_weight_bytes(J) = 3 * 2 * 64 * 8 * 2 bytes: bf16 weights as
+ *                  [layer l 0..2][m 0..1][lane 0..63][j 0..7] = W_(l+1)[16 m + (lane & 15)][kslot_l(8 (lane >> 4) + j)]
+ *                  with kslot_0(k) = k (the input channel) and, for l = 1, 2,
+ *                  kslot_l(8 g + j) = 16 (j >> 2) + 4 g + (j & 3) (the hidden channel an MFMA
+ *                  leaves in that lane); rows >= J of W_3 are zero
+ *   scale_shift    [2 layers][scale 32 | shift 32] f32: BN and conv bias folded,
+ *                  h = relu(conv * scale + shift)
+ *   bias3          (J) f32
+ *   out            (B, J, Vx, Vy, Vz) out_dtype (f32 | bf16): the logits, without the model's
+ *                  volume_multiplier (mvn_softargmax3d fuses it)
+ * The volume need not be cubic.  When Vx*Vy*Vz is no multiple of 4, or x or out is not 16-byte
+ * aligned, loads and stores are per element (the same result).
+ * MVN_ERR_ARG for a null pointer or an unknown layout; MVN_ERR_DTYPE for an unknown dtype or f32
+ * with NDHWC; MVN_ERR_SHAPE for J outside 1..32, a non-positive extent or an overflowing element
+ * count.  Stream-ordered, allocates nothing, reentrant.
+ */
+size_t mvn_v2v_head_packed_weight_bytes(int J);
+int mvn_v2v_head(const void* x, int x_dtype, int x_layout, const void* weight_packed,
+                 const float* scale_shift, const float* bias3, void* out, int out_dtype,
+                 int B, int J, int Vx, int Vy, int Vz, void* stream);
+
+/*
+ * The end of the volumetric forward in one call: mvn_v2v_head into logits held in `workspace`,
+ * then mvn_softargmax3d (coords) or mvn_softargmax3d_cuboid (cuboids; then Vx = Vy = Vz) on
+ * them, over groups of `group_frames` frames (<= 0: the default, one group's f32 logits within
+ * half of the 256 MiB MALL, at most 64: 7 frames at 64^3 with J = 17).  Replaces
+ * triangulation.py:352-353 from back_layers[1] on.  Exactly one of coords (B, Vx, Vy, Vz, 3) and
+ * cuboids (B, MVN_CUBOID_FLOATS) is non-NULL.
+ *   multiplier, softmax, out_xyz (B, J, 3) f32, out_vol (B, J, Vx, Vy, Vz) out_dtype or NULL
+ *   (not wanted): as mvn_softargmax3d.
+ *   The logits are f32, except when a bf16 out_vol is wanted: the soft-argmax writes a bf16
+ *   volume from bf16 logits only, so the logits are then bf16.  Bit-identical to mvn_v2v_head
+ *   with those logits followed by the soft-argmax call, both on the whole batch.
+ *   workspace >= mvn_v2v_head_softargmax_workspace_bytes(group_frames, J, Vx, Vy, Vz) bytes
+ *   = G * J * Vx*Vy*Vz * 4 rounded up to 16, + mvn_softargmax3d_workspace_bytes(G, J, Vx, Vy, Vz),
+ *   G the group size; 16-byte aligned, contents need no initialisation.
+ * Errors as mvn_v2v_head, and MVN_ERR_ARG for both or neither of coords / cuboids or a flag
+ * other than 0 / 1, MVN_ERR_SHAPE for a non-cubic volume with cuboids, MVN_ERR_WORKSPACE for a
+ * missing or too small workspace.
+ */
+size_t mvn_v2v_head_softargmax_workspace_bytes(int group_frames, int J, int Vx, int Vy, int Vz);
+int mvn_v2v_head_softargmax(const void* x, int x_dtype, int x_layout, const void* weight_packed,
+                            const float* scale_shift, const float* bias3,
+                            const float* coords, const float* cuboids, int transfer_cmu,
+                            float multiplier, int softmax, float* out_xyz, void* out_vol, int out_dtype,
+                            void* workspace, size_t workspace_bytes, int group_frames,
+                            int B, int J, int Vx, int Vy, int Vz, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

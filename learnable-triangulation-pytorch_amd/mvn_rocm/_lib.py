@@ -58,6 +58,13 @@ SIGNATURES = {
                                             _c_void_p, _c_size_t, _c_int] + [_c_int] * 6 + [_c_void_p]),
     "mvn_v2v_front_packed_weight_bytes": (_c_size_t, []),
     "mvn_v2v_front": (_c_int, [_c_void_p] * 5 + [_c_int, _c_int, _c_int, _c_void_p]),
+    "mvn_v2v_head_packed_weight_bytes": (_c_size_t, [_c_int]),
+    "mvn_v2v_head": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int]
+                     + [_c_int] * 5 + [_c_void_p]),
+    "mvn_v2v_head_softargmax_workspace_bytes": (_c_size_t, [_c_int] * 5),
+    "mvn_v2v_head_softargmax": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                         _c_void_p, _c_int, _c_float, _c_int, _c_void_p, _c_void_p, _c_int,
+                                         _c_void_p, _c_size_t, _c_int] + [_c_int] * 5 + [_c_void_p]),
     "mvn_unproject_backward": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
                                         _c_void_p, _c_void_p] + [_c_int] * 8 + [_c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward_workspace_bytes": (_c_size_t, [_c_int] * 5),

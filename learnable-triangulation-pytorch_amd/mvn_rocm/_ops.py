@@ -205,6 +205,72 @@ def _(vol, cuboids, transfer, softmax, multiplier, return_volume, out_dtype):
     return vol.new_empty((B, J, 3), dtype=torch.float32), vol.new_empty(shape, dtype=_CODE_DTYPE[out_dtype])
 
 
+# --------------------------------------------------------------------------- V2V head
+def _head_dims(x: Tensor, channels_last: bool):
+    """(B, (Vx, Vy, Vz)) of the head's input in either layout."""
+    return x.shape[0], (tuple(x.shape[1:4]) if channels_last else tuple(x.shape[2:5]))
+
+
+@_op("v2v_head")
+def v2v_head(x: Tensor, packed: Tensor, scale_shift: Tensor, bias3: Tensor, out_dtype: int,
+             channels_last: bool) -> Tensor:
+    """x (B,32,Vx,Vy,Vz) f32|bf16, or (B,Vx,Vy,Vz,32) bf16 with channels_last -> logits
+    (B,J,Vx,Vy,Vz) of dtype code `out_dtype`, J = bias3.numel() (csrc/v2v_head.hip)."""
+    _require_gpu(x, packed, scale_shift, bias3)
+    (B, (Vx, Vy, Vz)), J = _head_dims(x, channels_last), bias3.numel()
+    out = torch.empty((B, J, Vx, Vy, Vz), dtype=_CODE_DTYPE[out_dtype], device=x.device)
+    if out.numel() == 0:                  # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_v2v_head(
+        x.data_ptr(), _DTYPE_CODE[x.dtype], _lib.MVN_LAYOUT_NDHWC if channels_last else _lib.MVN_LAYOUT_NCDHW,
+        packed.data_ptr(), scale_shift.data_ptr(), bias3.data_ptr(), out.data_ptr(), out_dtype, B, J, Vx, Vy, Vz,
+        _stream(x))
+    _lib.check(code, "mvn_v2v_head")
+    return out
+
+
+@v2v_head.register_fake
+def _(x, packed, scale_shift, bias3, out_dtype, channels_last):
+    B, vol = _head_dims(x, channels_last)
+    return x.new_empty((B, bias3.numel(), *vol), dtype=_CODE_DTYPE[out_dtype])
+
+
+@_op("v2v_head_softargmax")
+def v2v_head_softargmax(x: Tensor, packed: Tensor, scale_shift: Tensor, bias3: Tensor, coords: Optional[Tensor],
+                        cuboids: Optional[Tensor], transfer: bool, softmax: bool, multiplier: float,
+                        return_volume: bool, out_dtype: int, group_frames: int,
+                        channels_last: bool) -> Tuple[Tensor, Tensor]:
+    """v2v_head then the 3D soft-argmax in one C call (mvn_v2v_head_softargmax): exactly one of
+    coords (B,Vx,Vy,Vz,3) f32 and cuboids (B,18) f32 -> (xyz (B,J,3) f32, normalised volume or
+    an empty tensor when return_volume is False)."""
+    _require_gpu(x, packed, scale_shift, bias3, coords, cuboids)
+    (B, (Vx, Vy, Vz)), J = _head_dims(x, channels_last), bias3.numel()
+    xyz = torch.empty((B, J, 3), dtype=torch.float32, device=x.device)
+    shape = (B, J, Vx, Vy, Vz) if return_volume else (0,)
+    out = torch.empty(shape, dtype=_CODE_DTYPE[out_dtype], device=x.device)
+    if xyz.numel() == 0:
+        return xyz, out
+    lib = _lib.load()
+    ws_bytes = lib.mvn_v2v_head_softargmax_workspace_bytes(int(group_frames), J, Vx, Vy, Vz)
+    ws = torch.empty((ws_bytes + 15) // 16 * 4, dtype=torch.float32, device=x.device)
+    code = lib.mvn_v2v_head_softargmax(
+        x.data_ptr(), _DTYPE_CODE[x.dtype], _lib.MVN_LAYOUT_NDHWC if channels_last else _lib.MVN_LAYOUT_NCDHW,
+        packed.data_ptr(), scale_shift.data_ptr(), bias3.data_ptr(), _ptr(coords), _ptr(cuboids), int(transfer),
+        float(multiplier), int(softmax), xyz.data_ptr(), out.data_ptr() if return_volume else None, out_dtype,
+        ws.data_ptr(), ws.numel() * 4, int(group_frames), B, J, Vx, Vy, Vz, _stream(x))
+    _lib.check(code, "mvn_v2v_head_softargmax")
+    return xyz, out
+
+
+@v2v_head_softargmax.register_fake
+def _(x, packed, scale_shift, bias3, coords, cuboids, transfer, softmax, multiplier, return_volume, out_dtype,
+      group_frames, channels_last):
+    B, vol = _head_dims(x, channels_last)
+    J = bias3.numel()
+    shape = (B, J, *vol) if return_volume else (0,)
+    return x.new_empty((B, J, 3), dtype=torch.float32), x.new_empty(shape, dtype=_CODE_DTYPE[out_dtype])
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,

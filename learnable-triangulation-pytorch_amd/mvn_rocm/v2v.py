@@ -7,6 +7,10 @@ unprojected volume (triangulation.py:352).  In eval mode the block is one MFMA k
 the volume channels-last in bf16 straight from the unprojection
 (``unproject_channels_last``): the unproject + view-softmax + front-block pipeline of
 config 5 is two launches and one (B, V^3, 32) bf16 intermediate.
+
+The other end of the V2V, its pointwise tail ``back_layers[1]``, ``back_layers[2]`` and
+``output_layer`` (v2v.py:154-160), is ``v2v_head`` / ``V2VHead`` below (csrc/v2v_head.hip,
+DESIGN.md §4.11), alone or in one call with the 3D soft-argmax behind it.
 """
 from __future__ import annotations
 
@@ -61,15 +65,15 @@ def v2v_front(vol_cl, packed, scale, shift, out_dtype=torch.float32):
     return out
 
 
-def _inference_only(what, *tensors):
+def _inference_only(what, *tensors, instead=None):
     """The channels-last unprojection and the fused V2V front block have no backward: refuse
     a call autograd would record (ADVICE r5 — a 'conf*' training caller would otherwise get a
     volume without grad and lose the confidence gradient silently).  Training goes through
     ``op.unproject_heatmaps`` (differentiable in the features and the confidences)."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
         raise RuntimeError(f"{what} is inference-only (no backward): call it under torch.no_grad(), or use "
-                           "mvn_rocm.op.unproject_heatmaps, which is differentiable in the features and the "
-                           "confidences")
+                           + (instead or "mvn_rocm.op.unproject_heatmaps, which is differentiable in the features "
+                              "and the confidences"))
 
 
 def unproject_channels_last(heatmaps, proj_matricies, coord_volumes, volume_aggregation_method="softmax",
@@ -206,3 +210,150 @@ def unproject_v2v_front(heatmaps, proj_matricies, coord_volumes, packed, scale, 
                                           _stream(feat))
     _lib.check(code, "mvn_unproject_v2v_front_ex")
     return out
+
+
+# --------------------------------------------------------------------------- V2V head
+# The pointwise tail of V2VModel (mvn/models/v2v.py:154-160): back_layers[1], back_layers[2]
+# (Basic3DBlock(32, 32, 1)) and output_layer (Conv3d(32, J, 1)) as one kernel
+# (csrc/v2v_head.hip), optionally with the 3D soft-argmax behind it.
+HEAD_C = 32
+
+
+def head_kslot(layer):
+    """K-slot -> input channel of the packed weights of ``layer`` (0, 1, 2): the identity for the
+    first layer; for the others slot 8g + j holds hidden channel 16 (j >> 2) + 4g + (j & 3), the
+    channel an MFMA result leaves in that lane (mvn_hip.h, mvn_v2v_head)."""
+    k = torch.arange(HEAD_C)
+    if layer == 0:
+        return k
+    g, j = k // 8, k % 8
+    return 16 * (j // 4) + 4 * g + (j % 4)
+
+
+def _fold_bn(conv, bn, what):
+    """(f64 weight (32, 32), f64 scale, f64 shift) of an eval-mode Conv3d(32, 32, 1) + BatchNorm3d."""
+    w = conv.weight.detach().to(torch.float64).cpu()
+    if tuple(w.shape) != (HEAD_C, HEAD_C, 1, 1, 1):
+        raise RuntimeError(f"{what}: expected a ({HEAD_C}, {HEAD_C}, 1, 1, 1) Conv3d weight, got {tuple(w.shape)}")
+    if bn.running_mean is None or tuple(bn.running_mean.shape) != (HEAD_C,):
+        raise RuntimeError(f"{what}: expected a BatchNorm3d({HEAD_C}) with running statistics")
+    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(HEAD_C, dtype=torch.float64)
+    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
+    return w.reshape(HEAD_C, HEAD_C), s, shift
+
+
+def fold_v2v_head(block1, block2, output_conv, device="cuda"):
+    """Two eval-mode ``Basic3DBlock(32, 32, 1)``-shaped modules (``.block[0]`` conv, ``.block[1]``
+    BN) and a ``Conv3d(32, J, 1)`` -> (packed bf16 weights, scale_shift (2, 2, 32) f32, bias3 (J,)
+    f32) on ``device``.  BN and the conv bias are folded in float64 as in ``fold_basic3d_block``;
+    the weights are rounded to bf16 and packed [layer][m][lane][8] as mvn_v2v_head expects."""
+    w1, s1, t1 = _fold_bn(block1.block[0], block1.block[1], "block1")
+    w2, s2, t2 = _fold_bn(block2.block[0], block2.block[1], "block2")
+    w3 = output_conv.weight.detach().to(torch.float64).cpu()
+    J = w3.shape[0]
+    if w3.dim() != 5 or tuple(w3.shape[1:]) != (HEAD_C, 1, 1, 1) or not 1 <= J <= HEAD_C:
+        raise RuntimeError(f"output_conv: expected a (J <= {HEAD_C}, {HEAD_C}, 1, 1, 1) Conv3d weight, "
+                           f"got {tuple(w3.shape)}")
+    w3p = torch.zeros(HEAD_C, HEAD_C, dtype=torch.float64)
+    w3p[:J] = w3.reshape(J, HEAD_C)
+    b3 = output_conv.bias.detach().double().cpu() if output_conv.bias is not None else torch.zeros(J, dtype=torch.float64)
+    lane = torch.arange(64)
+    row, k = lane % 16, (lane // 16).view(64, 1) * 8 + torch.arange(8).view(1, 8)    # [lane], [lane][j]
+    packed = torch.empty(3, 2, 64, 8, dtype=torch.float64)
+    for l, w in enumerate((w1, w2, w3p)):
+        cin = head_kslot(l)[k]                                                       # [lane][j]
+        for m in range(2):
+            packed[l, m] = w[(16 * m + row).view(64, 1).expand(64, 8), cin]
+    packed = packed.to(torch.float32).to(torch.bfloat16).contiguous()
+    scale_shift = torch.stack([torch.stack([s1, t1]), torch.stack([s2, t2])]).float().contiguous()
+    dev = torch.device(device)
+    return packed.to(dev), scale_shift.to(dev), b3.float().to(dev)
+
+
+def _head_input(what, x, packed, scale_shift, bias3, channels_last):
+    """Checked, contiguous input of the head and its joint count."""
+    _inference_only(what, x, packed, scale_shift, bias3,
+                    instead="the model's own back_layers and output_layer, which autograd records")
+    _dtype_code(x.dtype)
+    ch = x.shape[-1] if channels_last else (x.shape[1] if x.dim() == 5 else -1)
+    if x.dim() != 5 or ch != HEAD_C:
+        want = f"(B, Vx, Vy, Vz, {HEAD_C})" if channels_last else f"(B, {HEAD_C}, Vx, Vy, Vz)"
+        raise RuntimeError(f"{what}: x must be {want}, got {tuple(x.shape)}")
+    if channels_last and x.dtype != torch.bfloat16:
+        raise TypeError(f"{what}: a channels-last x must be bfloat16, got {x.dtype}")
+    J = bias3.numel()
+    if (tuple(packed.shape) != (3, 2, 64, 8) or packed.dtype != torch.bfloat16 or tuple(scale_shift.shape) != (2, 2, HEAD_C)
+            or scale_shift.dtype != torch.float32 or bias3.dtype != torch.float32 or not 1 <= J <= HEAD_C):
+        raise RuntimeError(f"{what}: packed, scale_shift, bias3 must be what fold_v2v_head returns")
+    return x.contiguous(), packed.contiguous(), scale_shift.contiguous(), bias3.contiguous()
+
+
+def v2v_head(x, packed, scale_shift, bias3, out_dtype=torch.float32, channels_last=False):
+    """(B, 32, Vx, Vy, Vz) f32 | bf16 — or (B, Vx, Vy, Vz, 32) bf16 with ``channels_last`` — ->
+    the logits (B, J, Vx, Vy, Vz) of back_layers[1], back_layers[2] and output_layer
+    (v2v.py:154-160, eval mode), without the model's volume multiplier.  Inference-only."""
+    from . import _ops
+    od = _dtype_code(out_dtype)
+    x, packed, scale_shift, bias3 = _head_input("v2v_head", x, packed, scale_shift, bias3, channels_last)
+    return _ops.call(_ops.v2v_head, x, packed, scale_shift, bias3, od, bool(channels_last))
+
+
+def v2v_head_softargmax(x, packed, scale_shift, bias3, coord_volumes, softmax=True, multiplier=1.0, out_dtype=None,
+                        return_volumes=True, group_frames=0, channels_last=False):
+    """``v2v_head`` then ``op.integrate_tensor_3d_with_coordinates(logits, coord_volumes, softmax,
+    multiplier=multiplier)`` in one call (``mvn_v2v_head_softargmax``), pipelined over groups of
+    ``group_frames`` frames through a workspace of one group's logits (default: within half of
+    the MALL, 7 frames at 64^3 with J = 17).  Returns (keypoints (B, J, 3), volumes or None), the
+    convention of ``op.integrate_tensor_3d_with_coordinates``; ``coord_volumes`` may be a
+    ``volumetric.Cuboids``.  ``out_dtype`` (default float32) is the dtype of the returned
+    volumes; a bfloat16 volume is formed from bfloat16 logits (the soft-argmax has no f32 ->
+    bf16 form), everything else from float32 logits.  Equal bit for bit to the two steps with
+    those logits.  Inference-only."""
+    from . import _ops
+    from .volumetric import Cuboids
+    od = _dtype_code(out_dtype if out_dtype is not None else torch.float32)
+    x, packed, scale_shift, bias3 = _head_input("v2v_head_softargmax", x, packed, scale_shift, bias3, channels_last)
+    B, vol = _ops._head_dims(x, channels_last)
+    if isinstance(coord_volumes, Cuboids):
+        cub = coord_volumes
+        if cub.shape != (B, *vol, 3):
+            raise RuntimeError(f"cuboids {tuple(cub.shape)} do not match x {tuple(x.shape)}")
+        coords, params, transfer = None, cub.params, cub.transfer
+    else:
+        coords, params, transfer = _ops.f32c(coord_volumes), None, False
+        if tuple(coords.shape) != (B, *vol, 3):
+            raise RuntimeError(f"coord_volumes {tuple(coords.shape)} does not match x {tuple(x.shape)}")
+    xyz, out = _ops.call(_ops.v2v_head_softargmax, x, packed, scale_shift, bias3, coords, params, bool(transfer),
+                         bool(softmax), float(multiplier), bool(return_volumes), od, int(group_frames),
+                         bool(channels_last))
+    return xyz, (out if return_volumes else None)
+
+
+class V2VHead(nn.Module):
+    """Eval-mode replacement of V2VModel's back_layers[1], back_layers[2] and output_layer with
+    the 3D soft-argmax behind them: ``V2VHead.from_reference(m)(v2v_trunk(m, volumes),
+    coord_volumes, volume_multiplier)`` replaces triangulation.py:352-353."""
+
+    def __init__(self, packed, scale_shift, bias3):
+        super().__init__()
+        self.register_buffer("packed", packed)
+        self.register_buffer("scale_shift", scale_shift)
+        self.register_buffer("bias3", bias3)
+
+    @classmethod
+    def from_reference(cls, v2v_model, device="cuda"):
+        return cls(*fold_v2v_head(v2v_model.back_layers[1], v2v_model.back_layers[2], v2v_model.output_layer,
+                                  device=device))
+
+    def forward(self, x, coord_volumes, multiplier=1.0, softmax=True):
+        return v2v_head_softargmax(x, self.packed, self.scale_shift, self.bias3, coord_volumes, softmax=softmax,
+                                   multiplier=multiplier)
+
+
+def v2v_trunk(v2v_model, x):
+    """V2VModel.forward (v2v.py:164-169) up to the head: front_layers, encoder_decoder and
+    back_layers[0], run with the model's own modules."""
+    x = v2v_model.front_layers(x)
+    x = v2v_model.encoder_decoder(x)
+    return v2v_model.back_layers[0](x)

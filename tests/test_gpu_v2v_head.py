@@ -1,0 +1,359 @@
+"""V2V head (csrc/v2v_head.hip): back_layers[1], back_layers[2] and output_layer of V2VModel
+(mvn/models/v2v.py:154-160, eval mode) as one bf16 MFMA kernel, alone and with the 3D
+soft-argmax behind it (mvn_v2v_head_softargmax).
+
+The logits are checked against a restatement written here, in torch on the CPU, in float64 with
+the kernel's own roundings: x, the weights and both hidden activations rounded to bf16, scale and
+shift the f32 values of the fold.  The kernel differs from it only by the f32 accumulation order
+and by the rare hidden activation that order pushes across a bf16 rounding boundary, hence three
+conditions (none of them taken from what the kernel gives):
+  tight  |got - ref| <= 1e-4 max|ref|  (the front block's bar, tests/test_gpu_configs.py)
+  loose  every element within 2^-8 max|ref| (one bf16 step of the largest logit)
+  cap    at most 0.5 % of the voxels exceed the tight bar on any of their J logits
+The cap's evidence is the same restatement in f32 against f64 (CPU only; unit-normal input,
+Xavier-scale weights): 0.012 % of 32,768 voxels exceed the tight bar, the worst by 4.0e-4
+max|ref|; at 210 voxels none.  Every case asserts the cap on that CPU pair too, so a bad choice of
+inputs shows up as such.  Reads nothing outside the repository.
+"""
+import numpy as np
+import pytest
+import torch
+from torch import nn
+
+from conftest import assert_bits_equal, max_rel
+
+TIGHT, LOOSE, CAP = 1e-4, 2.0 ** -8, 0.005
+C = 32
+
+
+# ---------------------------------------------------------------- stand-ins and the restatement
+class Basic3DBlock(nn.Module):
+    """The reference's Basic3DBlock (v2v.py:7-17), from torch.nn."""
+
+    def __init__(self, cin, cout, k):
+        super().__init__()
+        self.block = nn.Sequential(nn.Conv3d(cin, cout, k, 1, (k - 1) // 2), nn.BatchNorm3d(cout), nn.ReLU(True))
+
+    def forward(self, x):
+        return self.block(x)
+
+
+def make_head(J, seed, dead_channel=False):
+    """(block1, block2, output_conv) in eval mode: Xavier-normal weights (v2v.py:171-176), small
+    biases, BatchNorm statistics of a trained layer's order of magnitude.  ``dead_channel``: the
+    BN shift of hidden channel 5 of both blocks is so negative that relu kills it everywhere."""
+    g = torch.Generator().manual_seed(seed)
+    blocks = [Basic3DBlock(C, C, 1), Basic3DBlock(C, C, 1)]
+    out = nn.Conv3d(C, J, 1)
+    with torch.no_grad():
+        for conv in (blocks[0].block[0], blocks[1].block[0], out):
+            fan = conv.weight.shape[0] + conv.weight.shape[1]
+            conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * (2.0 / fan) ** 0.5)
+            conv.bias.copy_(torch.randn(conv.bias.shape, generator=g) * 0.1)
+        for blk in blocks:
+            bn = blk.block[1]
+            bn.weight.copy_(0.75 + 0.5 * torch.rand(C, generator=g))
+            bn.bias.copy_(0.2 * torch.randn(C, generator=g))
+            bn.running_mean.copy_(0.2 * torch.randn(C, generator=g))
+            bn.running_var.copy_(0.75 + 0.5 * torch.rand(C, generator=g))
+            if dead_channel:
+                bn.bias[5] = -1000.0
+    for m in (*blocks, out):
+        m.eval()
+    return blocks[0], blocks[1], out
+
+
+def bf16r(t):
+    """t rounded to bf16 (nearest-even, from its f32 value), as float64."""
+    return t.float().to(torch.bfloat16).double()
+
+
+def unpack(packed, layer):
+    """The (32, 32) bf16 weight matrix of ``layer`` from the documented packed layout
+    (mvn_hip.h): [layer][m][lane][j] = W[16 m + (lane & 15)][kslot(8 (lane >> 4) + j)]."""
+    W = torch.zeros(C, C, dtype=torch.float64)
+    p = packed.cpu().double()
+    for m in range(2):
+        for lane in range(64):
+            for j in range(8):
+                k = 8 * (lane >> 4) + j
+                g, jj = k // 8, k % 8
+                cin = k if layer == 0 else 16 * (jj >> 2) + 4 * g + (jj & 3)
+                W[16 * m + (lane & 15), cin] = p[layer, m, lane, j]
+    return W
+
+
+def restate(x, packed, scale_shift, bias3, dtype=torch.float64):
+    """x (B, 32, S) -> logits (B, J, S) in ``dtype``, with the kernel's roundings."""
+    J = bias3.numel()
+    W = [unpack(packed, l).to(dtype) for l in range(3)]
+    ss, b3 = scale_shift.cpu().to(dtype), bias3.cpu().to(dtype)
+    h = bf16r(x).to(dtype)
+    for l in range(2):
+        acc = torch.einsum("oc,bcs->bos", W[l], h)
+        h = bf16r(torch.relu(acc * ss[l, 0].view(1, C, 1) + ss[l, 1].view(1, C, 1))).to(dtype)
+    return torch.einsum("oc,bcs->bos", W[2][:J], h) + b3.view(1, J, 1)
+
+
+def exceed(got, ref):
+    """(fraction of voxels with a logit over the tight bar, worst error / max|ref|)."""
+    ref = ref.double()
+    err = (got.double() - ref).abs() / ref.abs().max()
+    return float((err > TIGHT).any(dim=1).double().mean()), float(err.max())
+
+
+def check_bars(got, x, params):
+    """The three conditions on ``got`` (B, J, S), and the cap on the f32-vs-f64 CPU pair."""
+    ref = restate(x, *params)
+    frac32, worst32 = exceed(restate(x, *params, dtype=torch.float32), ref)
+    frac, worst = exceed(got.cpu(), ref)
+    print(f"voxels over the tight bar: kernel {frac:.5f} (worst {worst:.2e}), f32 restatement {frac32:.5f} "
+          f"(worst {worst32:.2e}), of {ref.shape[0] * ref.shape[2]}")
+    assert frac32 <= CAP and worst32 <= LOOSE, "the inputs break the cap on the CPU f32-vs-f64 pair"
+    assert worst <= LOOSE
+    assert frac <= CAP
+
+
+LAYOUTS = ("ncdhw_f32", "ncdhw_bf16", "ndhwc_bf16")
+
+
+def as_layout(x, vol, layout, device):
+    """x (B, 32, S) f32 on the CPU -> (the kernel's input on the device, channels_last, x as the
+    kernel sees it (B, 32, S))."""
+    B = x.shape[0]
+    if layout == "ncdhw_f32":
+        return x.view(B, C, *vol).to(device), False, x
+    xb = x.to(torch.bfloat16)
+    if layout == "ncdhw_bf16":
+        return xb.view(B, C, *vol).to(device), False, xb.float()
+    return xb.view(B, C, *vol).permute(0, 2, 3, 4, 1).contiguous().to(device), True, xb.float()
+
+
+def run_head(x_dev, params, channels_last, out_dtype=torch.float32):
+    from mvn_rocm import v2v
+    with torch.no_grad():
+        y = v2v.v2v_head(x_dev, *params, out_dtype=out_dtype, channels_last=channels_last)
+    return y.reshape(y.shape[0], y.shape[1], -1)
+
+
+def fold(J, seed, device, dead_channel=False):
+    from mvn_rocm import v2v
+    return v2v.fold_v2v_head(*make_head(J, seed, dead_channel), device=device)
+
+
+# ---------------------------------------------------------------- logits against the restatement
+VOLUMES = ((8, 8, 8), (4, 4, 5), (5, 6, 7), (3, 5, 7))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("J", (1, 16, 17, 32))
+@pytest.mark.parametrize("vol", VOLUMES, ids=lambda v: "x".join(map(str, v)))
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_logits_match_the_restatement(device, layout, vol, J):
+    """B = 2; (8,8,8): whole chunks; (4,4,5): S % 4 == 0 with a ragged last chunk; (5,6,7):
+    S % 4 == 2 (per-element path); (3,5,7): S odd, frame 1's rows misaligned."""
+    params = fold(J, 100 + J, device)
+    S = vol[0] * vol[1] * vol[2]
+    x = torch.randn(2, C, S, generator=torch.Generator().manual_seed(S + J))
+    x_dev, cl, x_seen = as_layout(x, vol, layout, device)
+    got = run_head(x_dev, params, cl)
+    assert got.shape == (2, J, S) and got.dtype == torch.float32
+    check_bars(got, x_seen, params)
+    # bf16 logits: the f32 logits rounded by .to(torch.bfloat16), bit for bit
+    got16 = run_head(x_dev, params, cl, torch.bfloat16)
+    assert got16.dtype == torch.bfloat16
+    assert torch.equal(got16.view(torch.int16), got.to(torch.bfloat16).view(torch.int16))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_dead_hidden_channel(device, layout):
+    """BN shifts so negative that hidden channel 5 of both blocks is 0 at every voxel."""
+    params = fold(17, 7, device, dead_channel=True)
+    vol, S = (5, 6, 7), 210
+    x = torch.randn(2, C, S, generator=torch.Generator().manual_seed(3))
+    x_dev, cl, x_seen = as_layout(x, vol, layout, device)
+    check_bars(run_head(x_dev, params, cl), x_seen, params)
+
+
+# ---------------------------------------------------------------- no stray writes
+@pytest.mark.gpu
+@pytest.mark.parametrize("J,vol,pad", ((17, (5, 6, 7), 7), (1, (3, 5, 7), 5), (17, (4, 4, 5), 64)),
+                         ids=("J17-5x6x7", "J1-3x5x7", "J17-4x4x5-aligned"))
+@pytest.mark.parametrize("out_dtype", (torch.float32, torch.bfloat16), ids=("f32", "bf16"))
+def test_no_stray_writes(device, J, vol, pad, out_dtype):
+    """The C ABI with `out` a slice inside a sentinel-filled tensor: every sentinel before and
+    after the slice is intact, and the slice holds the logits."""
+    from mvn_rocm import _lib, _ops, v2v
+    params = fold(J, 11, device)
+    B, S = 2, vol[0] * vol[1] * vol[2]
+    x = torch.randn(B, C, *vol, generator=torch.Generator().manual_seed(5)).to(device)
+    n = B * J * S
+    big = torch.full((pad + n + 300,), -768.0, dtype=out_dtype, device=device)
+    code = _lib.load().mvn_v2v_head(x.data_ptr(), _lib.MVN_DTYPE_F32, _lib.MVN_LAYOUT_NCDHW, params[0].data_ptr(),
+                                    params[1].data_ptr(), params[2].data_ptr(),
+                                    big.data_ptr() + pad * big.element_size(), _ops._DTYPE_CODE[out_dtype], B, J,
+                                    *vol, _ops._stream(x))
+    assert code == 0
+    torch.cuda.synchronize()
+    assert (big[:pad] == -768.0).all() and (big[pad + n:] == -768.0).all()
+    with torch.no_grad():
+        want = v2v.v2v_head(x, *params, out_dtype=out_dtype)
+    assert torch.equal(big[pad:pad + n].view(torch.int16 if out_dtype == torch.bfloat16 else torch.int32),
+                       want.reshape(-1).view(torch.int16 if out_dtype == torch.bfloat16 else torch.int32))
+
+
+# ---------------------------------------------------------------- NaN and inf
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout,vol", (("ncdhw_f32", (8, 8, 8)), ("ncdhw_f32", (3, 5, 7)), ("ncdhw_bf16", (4, 4, 5)),
+                                        ("ndhwc_bf16", (5, 6, 7))))
+def test_nonfinite_voxels_follow_torch(device, layout, vol):
+    """One NaN, one +inf and one -inf voxel (one channel each) in x: exactly those voxels are NaN
+    or inf across all J, with torch's mask and values on the same bf16-rounded operands (relu
+    keeps a NaN); everything else is bit-equal to the run without them."""
+    J = 17
+    params = fold(J, 21, device)
+    S = vol[0] * vol[1] * vol[2]
+    x = torch.randn(2, C, S, generator=torch.Generator().manual_seed(9))
+    bad = x.clone()
+    spots = ((0, 3, 1, float("nan")), (0, 30, S - 1, float("inf")), (1, 12, S // 2, float("-inf")))
+    for b, ch, s, v in spots:
+        bad[b, ch, s] = v
+    clean = run_head(*as_layout(x, vol, layout, device)[:1], params, layout == "ndhwc_bf16").cpu()
+    x_dev, cl, seen = as_layout(bad, vol, layout, device)
+    got = run_head(x_dev, params, cl).cpu()
+    ref = restate(seen, *params, dtype=torch.float32)       # torch, f32, the same rounded operands
+    special = torch.zeros(2, S, dtype=torch.bool)
+    for b, _, s, _ in spots:
+        special[b, s] = True
+    nonfinite = ~torch.isfinite(got)
+    assert torch.equal(nonfinite.all(dim=1), special) and torch.equal(nonfinite.any(dim=1), special)
+    assert torch.equal(torch.isnan(got), torch.isnan(ref))
+    assert torch.equal(torch.isposinf(got), torch.isposinf(ref)) and torch.equal(torch.isneginf(got), torch.isneginf(ref))
+    keep = ~special.view(2, 1, S).expand_as(got)
+    assert torch.equal(got[keep].view(torch.int32), clean[keep].view(torch.int32))
+
+
+# ---------------------------------------------------------------- one call == two steps
+def _coords(kind, B, V, device):
+    from mvn_rocm import volumetric
+    base = np.array([[10.0, -20.0, 900.0], [-150.0, 40.0, 1000.0], [60.0, 5.0, 1100.0]])[:B]
+    cub = volumetric.build_cuboids(base, 2500.0, V, theta=[0.0, 0.7, 2.1][:B], device=device)
+    return cub if kind == "cuboids" else cub.coord_volumes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("softmax", (True, False), ids=("softmax", "relu"))
+@pytest.mark.parametrize("kind", ("dense", "cuboids"))
+@pytest.mark.parametrize("group_frames", (0, 1, 2))
+def test_one_call_equals_two_steps(device, group_frames, kind, softmax):
+    """v2v_head_softargmax == v2v_head then op.integrate_tensor_3d_with_coordinates, bit for bit:
+    B = 3 in groups of 3 (default), 1 and 2 (a ragged last group), dense coordinates and Cuboids,
+    both modes, volumes out in f32, in bf16 (from bf16 logits: the soft-argmax's only bf16 form)
+    and not requested."""
+    from mvn_rocm import op, v2v
+    B, J, V = 3, 17, 8
+    params = fold(J, 31, device)
+    x = torch.randn(B, C, V, V, V, generator=torch.Generator().manual_seed(13)).to(device)
+    coords = _coords(kind, B, V, device)
+    with torch.no_grad():
+        for vol_dtype in (torch.float32, torch.bfloat16, None):
+            ld = torch.bfloat16 if vol_dtype == torch.bfloat16 else torch.float32
+            logits = v2v.v2v_head(x, *params, out_dtype=ld)
+            kp_ref, vol_ref = op.integrate_tensor_3d_with_coordinates(logits, coords, softmax, multiplier=1.5,
+                                                                      return_volumes=vol_dtype is not None)
+            kp, vol = v2v.v2v_head_softargmax(x, *params, coords, softmax=softmax, multiplier=1.5, out_dtype=vol_dtype,
+                                              return_volumes=vol_dtype is not None, group_frames=group_frames)
+            assert_bits_equal(kp.cpu().numpy(), kp_ref.cpu().numpy())
+            if vol_dtype is None:
+                assert vol is None and vol_ref is None
+            else:
+                assert vol.dtype == vol_dtype and vol.shape == (B, J, V, V, V)
+                assert_bits_equal(vol.float().cpu().numpy(), vol_ref.float().cpu().numpy())
+
+
+@pytest.mark.gpu
+def test_empty_batch(device):
+    from mvn_rocm import v2v
+    params = fold(17, 31, device)
+    x = torch.zeros(0, C, 4, 4, 4, device=device)
+    with torch.no_grad():
+        assert v2v.v2v_head(x, *params).shape == (0, 17, 4, 4, 4)
+        kp, vol = v2v.v2v_head_softargmax(x, *params, torch.zeros(0, 4, 4, 4, 3, device=device))
+    assert kp.shape == (0, 17, 3) and vol.shape == (0, 17, 4, 4, 4)
+
+
+# ---------------------------------------------------------------- end to end
+class _Model(nn.Module):
+    """The attributes of V2VModel that V2VHead.from_reference reads."""
+
+    def __init__(self, blocks, out):
+        super().__init__()
+        self.back_layers = nn.Sequential(nn.Identity(), *blocks)
+        self.output_layer = out
+
+
+def blob_head(J, seed):
+    """A head whose logits are blob-like when x's first J channels are: near-identity layers
+    (diagonal 1, Xavier-scale off-diagonal noise at a tenth) with ordinary BN statistics."""
+    b1, b2, out = make_head(J, seed)
+    with torch.no_grad():
+        for conv in (b1.block[0], b2.block[0], out):
+            w = conv.weight
+            w.mul_(0.1)
+            w[:, :, 0, 0, 0] += torch.eye(w.shape[0], C)
+    return b1, b2, out
+
+
+# twice the joints' max_rel measured on the MI355X
+E2E_BAR = 2 * 1.633e-3          # measured: max_rel 1.633e-3, max |error| 1.618e-3 of the 2500 mm cuboid side
+
+
+@pytest.mark.gpu
+def test_end_to_end_against_the_f32_modules(device):
+    """The true reference semantics: the unrounded f32 modules in eval mode on the CPU, then
+    torch's own soft-argmax (oracle/restate_torch.py), against V2VHead on the GPU, at
+    (16, 16, 16), J = 17, on blob-like logits (synth.blob_volumes feeds the first 17 input
+    channels, lifted by 4 so that the relus pass them).  This is where the bf16 operands cost
+    accuracy: measured 1.633e-3 max_rel of the joints (4.0 mm on a 2500 mm cuboid), above 1e-3 of
+    the cuboid side."""
+    from mvn_rocm import synth, v2v, volumetric
+    from oracle import restate_torch
+    B, J, V = 2, 17, 16
+    b1, b2, out = blob_head(J, 41)
+    coords = volumetric.build_coord_volumes(np.array([[10.0, -20.0, 900.0], [-150.0, 40.0, 1000.0]]), 2500.0, V,
+                                            theta=[0.0, 0.7], device=device)
+    blobs = synth.blob_volumes(coords, J, seed=4).cpu()
+    x = torch.cat([blobs + 4.0, torch.randn(B, C - J, V, V, V, generator=torch.Generator().manual_seed(2))], dim=1)
+    with torch.no_grad():
+        logits_ref = out(b2(b1(x)))
+        kp_ref, _ = restate_torch.integrate_tensor_3d_with_coordinates(logits_ref * 1.0, coords.cpu(), softmax=True)
+        head = v2v.V2VHead.from_reference(_Model((b1, b2), out), device=device)
+        kp, vol = head(x.to(device), coords, 1.0)
+    # the blobs survive the head: each joint's peak is well above its noise
+    assert float((logits_ref.amax(dim=(2, 3, 4)) - logits_ref.mean(dim=(2, 3, 4))).min()) > 4.0
+    rel = max_rel(kp.cpu().numpy(), kp_ref.numpy())
+    side = float(np.abs(kp.cpu().numpy() - kp_ref.numpy()).max()) / 2500.0
+    print(f"end to end: joints max_rel {rel:.3e}, max |error| {side:.3e} of the cuboid side")
+    assert rel <= E2E_BAR
+
+
+# ---------------------------------------------------------------- full size once
+@pytest.mark.gpu
+def test_full_size_64(device):
+    """64^3, B = 2, J = 17, NCDHW f32: the three bars, and the one-call keypoints equal to the
+    two-step path bit for bit."""
+    from mvn_rocm import op, v2v, volumetric
+    B, J, V = 2, 17, 64
+    params = fold(J, 51, device)
+    x = torch.randn(B, C, V ** 3, generator=torch.Generator().manual_seed(17))
+    x_dev = x.view(B, C, V, V, V).to(device)
+    got = run_head(x_dev, params, False)
+    check_bars(got, x, params)
+    coords = volumetric.build_coord_volumes(np.array([[10.0, -20.0, 900.0], [-150.0, 40.0, 1000.0]]), 2500.0, V,
+                                            theta=[0.0, 0.7], device=device)
+    with torch.no_grad():
+        kp_ref, _ = op.integrate_tensor_3d_with_coordinates(got.view(B, J, V, V, V), coords, True, multiplier=2.0,
+                                                            return_volumes=False)
+        kp, _ = v2v.v2v_head_softargmax(x_dev, *params, coords, multiplier=2.0, return_volumes=False)
+    assert_bits_equal(kp.cpu().numpy(), kp_ref.cpu().numpy())
