@@ -188,6 +188,13 @@ int mvn_unproject_precision(const void* feat, int feat_dtype,
  *                  [tap = (dx*7 + dy)*7 + dz][lane 0..63][j 0..7] = W[lane & 15][8*(lane >> 4) + j][dx][dy][dz]
  *   scale, shift   (16) f32: BN folded, y = relu(conv * scale + shift)
  *   out            (B, 16, V, V, V) out_dtype (f32 | bf16);  V % 16 == 0, V <= 256
+ * NaN follows torch: relu keeps a NaN (F.relu(NaN) = NaN, not 0), so a NaN or infinite input
+ * voxel reaches exactly its 7^3 neighbourhood (clipped at the volume border) in all 16 output
+ * channels, as F.relu(bn(conv(x))) does: NaN there for a NaN voxel; for an infinite one
+ * +inf or 0 by the sign of weight * scale (NaN where 0 * inf or inf - inf meet), and no other
+ * voxel or frame changes.  Checked before any HIP call: a NULL pointer (MVN_ERR_ARG), B < 1 or
+ * a V that is not a multiple of 16 in [16, 256] (MVN_ERR_SHAPE), another out_dtype
+ * (MVN_ERR_DTYPE).
  */
 size_t mvn_v2v_front_packed_weight_bytes(void);
 int mvn_v2v_front(const void* vol_cl, const void* weight_packed, const float* scale, const float* shift,

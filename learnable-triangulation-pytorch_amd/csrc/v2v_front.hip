@@ -295,11 +295,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
 
     // ---- epilogue: folded BN + ReLU, 4 consecutive z of one output channel per lane ----
+    // relu keeps a NaN as F.relu does (fmaxf returns 0 for one): a NaN input voxel shows in
+    // its 7^3 neighbourhood instead of vanishing
 #pragma unroll
     for (int m = 0; m < TY; ++m) {
       float y[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) y[i] = fmaxf(__builtin_fmaf(sum[m][i], s, sh), 0.f);
+      for (int i = 0; i < 4; ++i) y[i] = relu_keep_nan(__builtin_fmaf(sum[m][i], s, sh));
       TO* o = out + (((size_t(b) * CO + co) * V + (x0 + w)) * V + (y0 + m)) * V + z0 + zr;
       if constexpr (sizeof(TO) == 4) {
         *reinterpret_cast<float4*>(o) = make_float4(y[0], y[1], y[2], y[3]);

@@ -47,7 +47,12 @@ def fold_basic3d_block(weight, bias, bn_weight, bn_bias, running_mean, running_v
 
 
 def v2v_front(vol_cl, packed, scale, shift, out_dtype=torch.float32):
-    """(B, V, V, V, 32) bf16 channels-last -> (B, 16, V, V, V) relu(bn(conv3d_7(x)))."""
+    """(B, V, V, V, 32) bf16 channels-last -> (B, 16, V, V, V) relu(bn(conv3d_7(x))).
+
+    V is a multiple of 16 up to 256; a non-contiguous ``vol_cl`` is copied.  Non-finite voxels
+    follow torch: the relu keeps a NaN as ``F.relu`` does, so a NaN or infinite input voxel
+    reaches exactly its 7^3 neighbourhood (all 16 channels), as ``F.relu(bn(conv(x)))`` does,
+    and nothing else."""
     if vol_cl.dtype != torch.bfloat16 or vol_cl.dim() != 5 or vol_cl.shape[-1] != CIN:
         raise RuntimeError(f"vol_cl must be (B, V, V, V, {CIN}) bfloat16, got {tuple(vol_cl.shape)} {vol_cl.dtype}")
     B, V = vol_cl.shape[0], vol_cl.shape[1]
@@ -163,7 +168,9 @@ def unproject_v2v_front(heatmaps, proj_matricies, coord_volumes, packed, scale, 
     written channels-last bf16, then the front block relu(bn(conv3d_7)), pipelined over frame
     groups through a workspace of one group's intermediate (default: 8 frames at V = 64,
     within half of the MALL).  ``coord_volumes`` may be a ``volumetric.Cuboids``.  Equal to
-    ``v2v_front(unproject_channels_last(...))`` bit for bit.  'conf*' aggregation reads
+    ``v2v_front(unproject_channels_last(...))`` bit for bit, NaN included: a NaN voxel coming out
+    of the unprojection is NaN in its 7^3 neighbourhood of the result (``v2v_front``), not 0.
+    'conf*' aggregation reads
     ``vol_confidences`` (B, N, C), as the volumetric model does (triangulation.py:349).
     Inference-only: no backward (the eval-mode BatchNorm fold is inference by construction).
     ``precision='fast'`` runs the two steps (the one-call C pipeline is the

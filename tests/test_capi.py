@@ -202,6 +202,20 @@ def test_unproject_v2v_front_argument_validation(lib):
     assert call_ex(agg=3, conf=1, ws=None) == -5         # (validated up to the workspace: no HIP call)
 
 
+def test_v2v_front_argument_validation(lib):
+    """mvn_v2v_front checks its own arguments before any HIP call: every pointer, B >= 1, V a
+    multiple of 16 in [16, 256], the output dtype."""
+    assert lib.mvn_v2v_front_packed_weight_bytes() == 343 * 64 * 16
+
+    def call(ptrs=(1, 1, 1, 1, 1), od=0, B=1, V=64):
+        return lib.mvn_v2v_front(*ptrs, od, B, V, None)
+    for i in range(5):                                   # vol_cl, weight_packed, scale, shift, out
+        assert call(ptrs=tuple(None if j == i else 1 for j in range(5))) == -1, i
+    for bad in (dict(B=0), dict(V=0), dict(V=8), dict(V=24), dict(V=272)):
+        assert call(**bad) == -2, bad
+    assert call(od=2) == -3
+
+
 def test_channels_last_conf_needs_confidences():
     """'conf*' on the channels-last and one-call config-5 paths needs vol_confidences, as
     unproject_heatmaps does (TypeError before any device work)."""
