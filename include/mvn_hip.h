@@ -25,6 +25,9 @@
  *   mvn_v2v_head         <- mvn/models/v2v.py:154-160 (back_layers[1], back_layers[2] and
  *                           output_layer: the pointwise tail, eval mode), and with the 3D
  *                           soft-argmax behind it mvn_v2v_head_softargmax
+ *   mvn_v2v_conv3, mvn_v2v_res3d
+ *                        <- mvn/models/v2v.py:20-42 (Res3DBlock at the full resolution:
+ *                           front_layers[1..3], skip_res1, back_layers[0]; eval mode)
  *   mvn_triangulate_ransac <-mvn/models/triangulation.py:54-128 (the RANSAC baseline's host
  *                           loop: hypotheses, inlier DLT, Huber refinement)
  *   mvn_reprojection_error <- mvn/utils/multiview.py:177-184 calc_reprojection_error_matrix(...)
@@ -288,6 +291,78 @@ int mvn_v2v_head_softargmax(const void* x, int x_dtype, int x_layout, const void
                             float multiplier, int softmax, float* out_xyz, void* out_vol, int out_dtype,
                             void* workspace, size_t workspace_bytes, int group_frames,
                             int B, int J, int Vx, int Vy, int Vz, void* stream);
+
+/*
+ * Full-resolution Res3DBlock convolution, eval mode (v2v.py:20-42): Conv3d(cin -> 32, k = 3,
+ * stride 1, zero padding 1) + BatchNorm3d, an optional residual, ReLU, on bf16 MFMA with f32
+ * accumulation, channels-last bf16 in and out.  Per output voxel and output channel co:
+ *   acc = sum over the 27 taps and cin input channels of x * w   (bf16 operands, f32
+ *         accumulation, summation order free; a tap outside the volume is zero and never
+ *         reads the neighbouring frame)
+ *   pre = fmaf(acc, scale[co], shift[co])
+ *   r   = pre                                               skip_mode MVN_SKIP_NONE
+ *       = pre + float(skip[voxel][co])                      MVN_SKIP_IDENTITY
+ *       = pre + fmaf(acc_s, skip_scale[co], skip_shift[co]) MVN_SKIP_POINTWISE, acc_s the
+ *         1x1x1 conv of skip[voxel][0..15] with skip_weight_packed (bf16 operands, f32)
+ *   y   = bf16(r <= 0 ? +0 : r), nearest-even; a NaN r stays NaN (F.relu)
+ * each fmaf and the add one f32 rounding.
+ *   x              (B, V, V, V, cin) bf16, cin 16 | 32;  V % 16 == 0, 16 <= V <= 256
+ *   weight_packed  mvn_v2v_conv3_packed_weight_bytes(cin) = 27 * 2 * 64 * 8 * 2 bytes (either
+ *                  cin): bf16 weights as
+ *                  [tap = (dx*3 + dy)*3 + dz][m 0..1][lane 0..63][j 0..7]
+ *                    = W[16 m + (lane & 15)][8 (lane >> 4) + j][dx][dy][dz]
+ *                  (W the Conv3d weight (32, cin, 3, 3, 3); tap (dx, dy, dz) multiplies input
+ *                  voxel (x + dx - 1, y + dy - 1, z + dz - 1)); for cin = 16 the elements with
+ *                  8 (lane >> 4) + j >= 16 are zero (K is zero-padded)
+ *   scale, shift   (32) f32: BN and the conv bias folded
+ *   skip           NONE: NULL.  IDENTITY: (B, V, V, V, 32) bf16, skip_cin 32.  POINTWISE:
+ *                  (B, V, V, V, 16) bf16, skip_cin 16.  Must not overlap out.
+ *   skip_weight_packed  POINTWISE only (NULL otherwise), mvn_v2v_conv3_skip_packed_weight_bytes(16)
+ *                  = 2 * 64 * 8 * 2 bytes: [m 0..1][lane 0..63][j 0..7]
+ *                    = Ws[16 m + (lane & 15)][8 (lane >> 4) + j], zero where 8 (lane >> 4) + j >= 16
+ *   skip_scale, skip_shift  POINTWISE only (NULL otherwise): (32) f32
+ *   out            (B, V, V, V, 32) bf16
+ * A NaN or infinite input voxel reaches exactly its clipped 3^3 neighbourhood in all 32
+ * channels, a non-finite skip voxel exactly its own voxel, as the stock modules' F.relu gives.
+ * Checked before any HIP call: MVN_ERR_ARG for a null required pointer, an unknown skip_mode or
+ * a skip / skip_weight_packed / skip_scale / skip_shift pointer that contradicts the mode
+ * (given where the mode takes none, missing where it needs one); MVN_ERR_SHAPE for B < 1, a V
+ * outside the multiples of 16 in [16, 256], a cin other than 16 / 32, a skip_cin other than 32
+ * with IDENTITY or other than 16 with POINTWISE (ignored with NONE).  The size functions return
+ * 0 for a cin they do not take.  Stream-ordered, allocates nothing, reentrant.
+ */
+#define MVN_SKIP_NONE      0
+#define MVN_SKIP_IDENTITY  1
+#define MVN_SKIP_POINTWISE 2
+size_t mvn_v2v_conv3_packed_weight_bytes(int cin);
+size_t mvn_v2v_conv3_skip_packed_weight_bytes(int cin);
+int mvn_v2v_conv3(const void* x, int cin, const void* weight_packed, const float* scale, const float* shift,
+                  int skip_mode, const void* skip, int skip_cin, const void* skip_weight_packed,
+                  const float* skip_scale, const float* skip_shift, void* out, int B, int V, void* stream);
+
+/*
+ * A whole Res3DBlock in one call: mvn_v2v_conv3 (cin -> 32, skip NONE) into the hidden volume
+ * held in `workspace`, then mvn_v2v_conv3 (32 -> 32) on it with the block's input x as the
+ * skip, over groups of `group_frames` frames (<= 0: the default, one group's hidden volume
+ * within half of the 256 MiB MALL, at most 64: 8 frames at V = 64).
+ *   skip_mode      MVN_SKIP_IDENTITY (cin 32, the block's empty skip_con) or MVN_SKIP_POINTWISE
+ *                  (cin 16, skip_con = Conv3d 1x1x1 + BatchNorm3d) with skip_weight_packed,
+ *                  skip_scale, skip_shift as mvn_v2v_conv3's
+ *   weight1_packed, scale1, shift1   the first conv (cin -> 32);  weight2_packed, scale2, shift2
+ *                  the second (32 -> 32), packed as mvn_v2v_conv3's
+ *   out            (B, V, V, V, 32) bf16; must not overlap x
+ *   workspace      >= mvn_v2v_res3d_workspace_bytes(group_frames, V) = G * V^3 * 32 * 2 bytes, G the
+ *                  group size (0 for a V the block does not take); 16-byte aligned, contents
+ *                  need no initialisation
+ * Bit-identical to the two launches on the whole batch.  Errors as mvn_v2v_conv3 (MVN_ERR_ARG
+ * also for MVN_SKIP_NONE; MVN_ERR_SHAPE for IDENTITY with cin 16 or POINTWISE with cin 32), and
+ * MVN_ERR_WORKSPACE for a missing or too small workspace.
+ */
+size_t mvn_v2v_res3d_workspace_bytes(int group_frames, int V);
+int mvn_v2v_res3d(const void* x, int cin, const void* weight1_packed, const float* scale1, const float* shift1,
+                  const void* weight2_packed, const float* scale2, const float* shift2, int skip_mode,
+                  const void* skip_weight_packed, const float* skip_scale, const float* skip_shift, void* out,
+                  void* workspace, size_t workspace_bytes, int group_frames, int B, int V, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

@@ -1,0 +1,435 @@
+// Full-resolution Res3DBlocks of the V2V on bf16 MFMA for gfx950: one 3x3x3 convolution
+// (stride 1, zero padding 1) with folded BatchNorm, an optional residual and ReLU per launch.
+//
+// Replaces, in eval mode, the two convolutions of Res3DBlock (mvn/models/v2v.py:20-42):
+//   res_branch = Conv3d(cin, 32, 3, padding 1), BatchNorm3d, ReLU, Conv3d(32, 32, 3, padding 1),
+//   BatchNorm3d;  skip_con = empty (cin == 32) or Conv3d(cin, 32, 1), BatchNorm3d;
+//   y = relu(res_branch(x) + skip_con(x))
+// as conv1 = relu(bn(conv(x))) (skip NONE) and conv2 = relu(bn(conv(h)) + skip) (skip IDENTITY
+// or POINTWISE).  Volumes are channels-last bf16 on both sides: (B, V, V, V, Cin) in,
+// (B, V, V, V, 32) out, the layout the next conv and the head (v2v_head.hip, NDHWC) read.
+//
+// Arithmetic per output voxel and channel co (include/mvn_hip.h, mvn_v2v_conv3):
+//   acc = sum over taps and input channels of x * w   (bf16 operands, f32 accumulation, MFMA)
+//   pre = fma(acc, scale[co], shift[co])
+//   r   = pre | pre + float(skip) | pre + fma(acc_s, scale_s[co], shift_s[co])
+//   y   = bf16(relu_keep_nan(r))
+//
+// MFMA v_mfma_f32_16x16x32_bf16 in the head's orientation: A = 16 output channels x 32 K-slots
+// (the tap's weights, packed [tap][m][lane][8], read from LDS), B = 32 K-slots x 16 voxels (16
+// z-consecutive voxels of the tap-shifted input, read from an LDS halo), D = 16 channels x 16
+// voxels: lane (c = lane & 15, g = lane >> 4) ends with channels 16 m + 4 g + i (i = 0..3) of
+// voxel column c, which is one 8-byte channels-last store per m.  Cin = 16 zero-pads K: the
+// K-slots 16..31 hold zero weights and the lanes g >= 2 feed zeros (never halo data, so a
+// non-finite voxel cannot meet a zero weight there).
+//
+// A block of 4 waves walks a column of 4 x 8 x 16 output tiles along x.  The 27 taps' weights
+// (55,296 B) are loaded into LDS once per block; the 6 x 10 x 18-voxel input halo (69,120 B
+// at Cin = 32, zero-filled outside the volume by the buffer resource's range check, as Conv3d's
+// padding does) is a ring of 6 x-slices, 4 new slices per tile, loaded into registers under
+// the tile's MFMAs and written to LDS once every wave is done with the slices they replace.
+// Wave w computes the tile's output rows y = 2 w, 2 w + 1 for all 4 x: 8 voxel columns x 2
+// channel halves = 16 accumulators; per dz it reads 18 A fragments and the 6 x 4 halo columns
+// its outputs touch, each B fragment feeding up to 12 MFMAs (432 MFMAs on 126 ds_read_b128
+// per wave and tile).
+// Arithmetic: 2 * 27 * 32 * 32 * V^3 flop per frame (14.5 GFLOP at V = 64, Cin = 32).
+#include <climits>
+
+#include "common.hpp"
+
+namespace mvn {
+namespace {
+
+constexpr int CO = 32, NTAP = 27;
+constexpr int TX = 4, TY = 8, TZ = 16;
+constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2;                 // 6, 10, 18
+constexpr int kWaves = 4, kThreads = kWaves * kWave;
+constexpr int kRows = TY / kWaves;                                   // output y-rows per wave: 2
+constexpr int kWChunks = NTAP * 2 * kWave;                           // 3456 chunks of 16 B: [tap][m][lane]
+constexpr uint32_t kOob = 0x80000000u;
+
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
+  const uint64_t a = reinterpret_cast<uint64_t>(base);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(a));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(a >> 32));
+  void* p = reinterpret_cast<void*>((uint64_t(hi) << 32) | lo);
+  return __builtin_amdgcn_make_buffer_rsrc(p, 0, int(__builtin_amdgcn_readfirstlane(bytes)), 0x00020000);
+}
+
+__device__ __forceinline__ f32x4_t mfma(const uint4& a, const uint4& b, f32x4_t c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c,
+                                                 0, 0, 0);
+}
+
+// LDS position of 16-byte channel chunk c of a halo voxel at halo z index hz.  Cin = 32 (four
+// chunks, 64-byte voxel pitch): v2v_front's swizzle, which spreads the 16 z-consecutive voxels
+// x 4 chunks of one B read over 16 distinct bank quads in every ds_read_b128 lane group.
+// Cin = 16 (two chunks): the 16 voxels are 512 contiguous bytes, conflict-free as they are.
+template <int CH>
+__device__ __forceinline__ int chunk_pos(int c, int hz) {
+  return CH == 4 ? (c ^ (((hz >> 2) & 1) << 1)) : c;
+}
+
+template <int CIN, int MODE>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void v2v_conv3(
+    const uint16_t* __restrict__ in, const uint4* __restrict__ wpk, const float* __restrict__ scale,
+    const float* __restrict__ shift, const uint16_t* __restrict__ skip, const uint4* __restrict__ wskip,
+    const float* __restrict__ scale_s, const float* __restrict__ shift_s, uint16_t* __restrict__ out, int V) {
+  constexpr int CH = CIN / 8;                                // 16-byte chunks per voxel record
+  constexpr int kSliceChunks = HY * HZ * CH;                 // 720 | 360 chunks per x-slice
+  constexpr int kSlotBytes = kSliceChunks * 16;              // 11,520 | 5,760 B
+  constexpr int kHaloChunks = HX * kSliceChunks;
+  constexpr int kStage = (TX * kSliceChunks + kThreads - 1) / kThreads;   // new-slice chunks per thread: 12 | 6
+  static_assert(kSliceChunks <= 1024, "the staging descriptor holds a 10-bit LDS index");
+  __shared__ uint4 wl[kWChunks];                             // the 27 taps' A fragments
+  __shared__ uint4 halo[kHaloChunks];                        // ring of HX x-slices: [slot][hy][hz][chunk]
+  const int t = threadIdx.x, lane = t & (kWave - 1);
+  const int w = __builtin_amdgcn_readfirstlane(t / kWave);
+  const int nTz = V / TZ, nTy = V / TY, nTx = V / TX;
+  // blocks: (frame, ty, tz), XCD-contiguous; each walks its column of nTx tiles along x
+  int L = xcd_remap(blockIdx.x, gridDim.x);
+  const int tz = L % nTz; L /= nTz;
+  const int ty = L % nTy; L /= nTy;
+  const int b = L;
+  const int y0 = ty * TY, z0 = tz * TZ;
+  const size_t nvox = size_t(V) * V * V;
+  // one frame per resource: a tap outside the volume reads zero, never the neighbouring frame
+  const __amdgpu_buffer_rsrc_t irs = make_rsrc(in + size_t(b) * nvox * CIN, uint32_t(nvox * CIN * 2));
+
+  for (int q = t; q < kWChunks; q += kThreads) wl[q] = wpk[q];
+
+  // halo chunk q of the slices gx0, gx0 + 1, ...: its global byte offset (kOob: zero) and its
+  // LDS index in the ring (slice gx sits in slot (gx + 1) mod HX)
+  auto chunk_src = [&](int gx0, int q, int total) -> uint32_t {
+    const int sl = q / kSliceChunks, rem = q - sl * kSliceChunks;
+    const int v = rem / CH, c = rem % CH;
+    const int hz = v % HZ, hy = v / HZ;
+    const int gx = gx0 + sl, gy = y0 + hy - 1, gz = z0 + hz - 1;
+    const bool ok = (q < total) & (unsigned(gx) < unsigned(V)) & (unsigned(gy) < unsigned(V)) &
+                    (unsigned(gz) < unsigned(V));
+    return ok ? uint32_t(((size_t(gx) * V + gy) * V + gz) * CIN * 2 + c * 16) : kOob;
+  };
+  auto chunk_dst = [&](int gx0, int q) -> int {
+    const int sl = q / kSliceChunks, rem = q - sl * kSliceChunks;
+    const int v = rem / CH, c = rem % CH;
+    return ((gx0 + sl + 1) % HX) * kSliceChunks + v * CH + chunk_pos<CH>(c, v % HZ);
+  };
+  auto ld_chunk = [&](uint32_t off) {
+    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(irs, off, 0, 0));
+  };
+  {  // the first tile's 6 slices gx = -1 .. 4
+    constexpr int kBatch = 6;
+    for (int i0 = 0; i0 * kThreads < kHaloChunks; i0 += kBatch) {
+      uint4 vals[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) vals[u] = ld_chunk(chunk_src(-1, t + (i0 + u) * kThreads, kHaloChunks));
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int q = t + (i0 + u) * kThreads;
+        MVN_DASSERT(q >= kHaloChunks || (chunk_dst(-1, q) >= 0 && chunk_dst(-1, q) < kHaloChunks));
+        if (q < kHaloChunks) halo[chunk_dst(-1, q)] = vals[u];
+      }
+    }
+  }
+
+  // Per-tile staging of chunk q = t + u * kThreads (u < kStage) of the 4 new slices: the
+  // in-slice part is tile-invariant and decoded once into a packed descriptor:
+  // bit 0 valid (q in range), bits 1-2 slice, bits 3-12 LDS index within the slot,
+  // bit 13 y/z inside the volume, bits 14-31 (gy * V + gz) * CH + c (V <= 256: 18 bits).
+  uint32_t sdesc[kStage];
+#pragma unroll
+  for (int u = 0; u < kStage; ++u) {
+    const int q = t + u * kThreads;
+    const int sl = q / kSliceChunks, rem = q - sl * kSliceChunks;
+    const int v = rem / CH, c = rem % CH;
+    const int hz = v % HZ, hy = v / HZ;
+    const int gy = y0 + hy - 1, gz = z0 + hz - 1;
+    const bool valid = q < TX * kSliceChunks;
+    const bool yz = (unsigned(gy) < unsigned(V)) & (unsigned(gz) < unsigned(V));
+    const int li = v * CH + chunk_pos<CH>(c, hz);
+    MVN_DASSERT(!valid || (sl >= 0 && sl < TX && li >= 0 && li < kSliceChunks));
+    MVN_DASSERT(!yz || uint32_t((gy * V + gz) * CH + c) < (1u << 18));
+    sdesc[u] = (valid ? 1u : 0u) | (uint32_t(sl & 3) << 1) | (uint32_t(li) << 3) |
+               (yz ? (1u << 13) | (uint32_t((gy * V + gz) * CH + c) << 14) : 0u);
+  }
+  auto stage_src = [&](int u, int gx0) -> uint32_t {
+    const uint32_t d = sdesc[u];
+    const int gx = gx0 + int((d >> 1) & 3u);
+    const bool ok = ((d & ((1u << 13) | 1u)) == ((1u << 13) | 1u)) & (unsigned(gx) < unsigned(V));
+    return ok ? uint32_t(gx) * uint32_t(V * V * CIN * 2) + (d >> 14) * 16u : kOob;
+  };
+
+  const int c = lane & 15, g = lane >> 4;
+  // byte offset, within a slot, of the lane's B chunk of halo row 2 w at z offset dz
+  uint32_t lo[3];
+#pragma unroll
+  for (int dz = 0; dz < 3; ++dz) {
+    const int hz = c + dz;
+    lo[dz] = uint32_t(((w * kRows * HZ + hz) * CH + chunk_pos<CH>(g & (CH - 1), hz)) * 16);
+  }
+  const bool kpad = CH == 2 && g >= 2;                       // K-slots 16..31 of a Cin = 16 operand: zero
+  const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+  float sc[2][4], sh[2][4], scs[2][4], shs[2][4];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int ch = 16 * m + 4 * g + i;
+      sc[m][i] = scale[ch];
+      sh[m][i] = shift[ch];
+      if constexpr (MODE == MVN_SKIP_POINTWISE) {
+        scs[m][i] = scale_s[ch];
+        shs[m][i] = shift_s[ch];
+      }
+    }
+  uint4 As[2];
+  if constexpr (MODE == MVN_SKIP_POINTWISE) {
+    As[0] = wskip[lane];
+    As[1] = wskip[kWave + lane];
+  }
+  const char* hbase = reinterpret_cast<const char*>(halo);
+
+  for (int tx = 0; tx < nTx; ++tx) {
+    __syncthreads();                          // the weights and the tile's slices are in LDS
+    const int x0 = tx * TX;
+    const bool more = tx + 1 < nTx;
+    const int gxn = x0 + TX + 1;              // next tile's new slices: gx = x0 + 5 .. x0 + 8
+    // in flight under the MFMAs: the next tile's 4 new slices and this tile's skip operands
+    uint4 sv[kStage];
+#pragma unroll
+    for (int u = 0; u < kStage; ++u) sv[u] = ld_chunk(more ? stage_src(u, gxn) : kOob);
+    // voxel (x0 + x, y0 + 2 w + yl, z0 + c) of the frame
+    auto vox = [&](int x, int yl) { return ((size_t(b) * V + (x0 + x)) * V + (y0 + w * kRows + yl)) * V + z0 + c; };
+    uint2 sk[TX][kRows][2];                   // IDENTITY: the lane's 2 x 4 skip channels
+    uint4 skb[TX][kRows];                     // POINTWISE: the lane's B chunk of the skip voxel
+#pragma unroll
+    for (int x = 0; x < TX; ++x)
+#pragma unroll
+      for (int yl = 0; yl < kRows; ++yl) {
+        if constexpr (MODE == MVN_SKIP_IDENTITY) {
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+            sk[x][yl][m] = *reinterpret_cast<const uint2*>(skip + vox(x, yl) * CO + 16 * m + 4 * g);
+        } else if constexpr (MODE == MVN_SKIP_POINTWISE) {
+          skb[x][yl] = *reinterpret_cast<const uint4*>(skip + vox(x, yl) * 16 + 8 * (g & 1));
+        }
+      }
+
+    uint32_t sb[HX];                          // slot of halo x index hx (gx = x0 - 1 + hx), bytes
+    const int s0 = x0 % HX;
+#pragma unroll
+    for (int hx = 0; hx < HX; ++hx) {
+      const int slot = s0 + hx >= HX ? s0 + hx - HX : s0 + hx;
+      MVN_DASSERT(slot >= 0 && slot < HX);
+      sb[hx] = uint32_t(slot * kSlotBytes);
+    }
+    f32x4_t acc[TX][kRows][2];
+#pragma unroll
+    for (int x = 0; x < TX; ++x)
+#pragma unroll
+      for (int yl = 0; yl < kRows; ++yl)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) acc[x][yl][m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // Per dz: the 9 (dx, dy) taps' A fragments, then the 6 x 4 halo columns (hx, hyl) at z
+    // offset dz; output (x, yl) takes tap (dx, dy) from column (x + dx, yl + dy).  Consecutive
+    // MFMAs go to different accumulators.
+#pragma unroll
+    for (int dz = 0; dz < 3; ++dz) {
+      uint4 A[3][3][2];
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+          for (int m = 0; m < 2; ++m) {
+            const int ai = (((dx * 3 + dy) * 3 + dz) * 2 + m) * kWave + lane;
+            MVN_DASSERT(ai >= 0 && ai < kWChunks);
+            A[dx][dy][m] = wl[ai];
+          }
+#pragma unroll
+      for (int hx = 0; hx < HX; ++hx)
+#pragma unroll
+        for (int hyl = 0; hyl < kRows + 2; ++hyl) {
+          const uint32_t off = sb[hx] + uint32_t(hyl * HZ * CH * 16) + lo[dz];
+          MVN_DASSERT(off + 16 <= uint32_t(kHaloChunks * 16));
+          uint4 Bv = *reinterpret_cast<const uint4*>(hbase + off);
+          if (kpad) Bv = zero4;
+#pragma unroll
+          for (int dx = 0; dx < 3; ++dx) {
+            const int x = hx - dx;
+            if (x < 0 || x >= TX) continue;
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+              const int yl = hyl - dy;
+              if (yl < 0 || yl >= kRows) continue;
+#pragma unroll
+              for (int m = 0; m < 2; ++m) acc[x][yl][m] = mfma(A[dx][dy][m], Bv, acc[x][yl][m]);
+            }
+          }
+        }
+    }
+
+    __syncthreads();                          // every wave is done with the halo: the dead slots take the next slices
+    if (more) {
+#pragma unroll
+      for (int u = 0; u < kStage; ++u) {
+        const uint32_t d = sdesc[u];
+        if (d & 1u) {
+          int slot = ((gxn + 1) % HX) + int((d >> 1) & 3u);
+          if (slot >= HX) slot -= HX;
+          const int li = slot * kSliceChunks + int((d >> 3) & 1023u);
+          MVN_DASSERT(li >= 0 && li < kHaloChunks);
+          halo[li] = sv[u];
+        }
+      }
+    }
+
+    // ---- epilogue: folded BN, residual, ReLU (NaN kept, as F.relu), bf16, channels-last ----
+#pragma unroll
+    for (int x = 0; x < TX; ++x)
+#pragma unroll
+      for (int yl = 0; yl < kRows; ++yl) {
+        f32x4_t accs[2];
+        if constexpr (MODE == MVN_SKIP_POINTWISE) {
+          const uint4 Bs = g >= 2 ? zero4 : skb[x][yl];
+          const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+          accs[0] = mfma(As[0], Bs, z);
+          accs[1] = mfma(As[1], Bs, z);
+        }
+        const size_t v = vox(x, yl);
+        MVN_DASSERT(v < size_t(gridDim.x / (nTy * nTz)) * nvox);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          float y[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            float r = __builtin_fmaf(acc[x][yl][m][i], sc[m][i], sh[m][i]);
+            if constexpr (MODE == MVN_SKIP_IDENTITY) {
+              const uint32_t pair = i < 2 ? sk[x][yl][m].x : sk[x][yl][m].y;
+              r = r + __uint_as_float((i & 1) ? (pair & 0xffff0000u) : (pair << 16));
+            } else if constexpr (MODE == MVN_SKIP_POINTWISE) {
+              r = r + __builtin_fmaf(accs[m][i], scs[m][i], shs[m][i]);
+            }
+            y[i] = relu_keep_nan(r);
+          }
+          *reinterpret_cast<uint2*>(out + v * CO + 16 * m + 4 * g) =
+              make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+        }
+      }
+  }
+}
+
+constexpr long long kDefaultGroupBytes = 128LL << 20;        // half the MALL
+
+int default_group(int V) {
+  const long long g = kDefaultGroupBytes / ((long long)V * V * V * CO * 2);
+  return g < 1 ? 1 : int(g > 64 ? 64 : g);
+}
+
+bool volume_ok(int V) { return V >= 16 && V <= 256 && V % 16 == 0; }
+
+// Argument checks of one launch (before any HIP call).
+int check_conv3(const void* x, int cin, const void* wpk, const float* scale, const float* shift, int skip_mode,
+                const void* skip, int skip_cin, const void* wskip, const float* scale_s, const float* shift_s,
+                const void* out, int B, int V) {
+  if (!x || !wpk || !scale || !shift || !out) return MVN_ERR_ARG;
+  if (skip_mode != MVN_SKIP_NONE && skip_mode != MVN_SKIP_IDENTITY && skip_mode != MVN_SKIP_POINTWISE)
+    return MVN_ERR_ARG;
+  const bool pw = wskip || scale_s || shift_s;
+  if (skip_mode == MVN_SKIP_NONE && (skip || pw)) return MVN_ERR_ARG;
+  if (skip_mode == MVN_SKIP_IDENTITY && (!skip || pw)) return MVN_ERR_ARG;
+  if (skip_mode == MVN_SKIP_POINTWISE && (!skip || !wskip || !scale_s || !shift_s)) return MVN_ERR_ARG;
+  if (B < 1 || !volume_ok(V) || (cin != 16 && cin != 32)) return MVN_ERR_SHAPE;
+  if (skip_mode == MVN_SKIP_IDENTITY && skip_cin != 32) return MVN_ERR_SHAPE;
+  if (skip_mode == MVN_SKIP_POINTWISE && skip_cin != 16) return MVN_ERR_SHAPE;
+  if ((long long)B * (V / TY) * (V / TZ) > INT_MAX) return MVN_ERR_SHAPE;
+  return MVN_OK;
+}
+
+template <int CIN>
+int launch_conv3(const void* x, const void* wpk, const float* scale, const float* shift, int skip_mode,
+                 const void* skip, const void* wskip, const float* scale_s, const float* shift_s, void* out, int B,
+                 int V, hipStream_t st) {
+  const int nblk = B * (V / TY) * (V / TZ);                  // one block per tile column along x
+  const auto* in = static_cast<const uint16_t*>(x);
+  const auto* wp = static_cast<const uint4*>(wpk);
+  const auto* sk = static_cast<const uint16_t*>(skip);
+  const auto* ws = static_cast<const uint4*>(wskip);
+  auto* o = static_cast<uint16_t*>(out);
+  if (skip_mode == MVN_SKIP_NONE)
+    v2v_conv3<CIN, MVN_SKIP_NONE><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V);
+  else if (skip_mode == MVN_SKIP_IDENTITY)
+    v2v_conv3<CIN, MVN_SKIP_IDENTITY><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V);
+  else
+    v2v_conv3<CIN, MVN_SKIP_POINTWISE><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V);
+  return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
+}
+
+int run_conv3(const void* x, int cin, const void* wpk, const float* scale, const float* shift, int skip_mode,
+              const void* skip, const void* wskip, const float* scale_s, const float* shift_s, void* out, int B, int V,
+              hipStream_t st) {
+  return cin == 16 ? launch_conv3<16>(x, wpk, scale, shift, skip_mode, skip, wskip, scale_s, shift_s, out, B, V, st)
+                   : launch_conv3<32>(x, wpk, scale, shift, skip_mode, skip, wskip, scale_s, shift_s, out, B, V, st);
+}
+
+}  // namespace
+}  // namespace mvn
+
+extern "C" size_t mvn_v2v_conv3_packed_weight_bytes(int cin) {
+  return cin == 16 || cin == 32 ? size_t(mvn::kWChunks) * 16 : 0;
+}
+
+extern "C" size_t mvn_v2v_conv3_skip_packed_weight_bytes(int cin) {
+  return cin == 16 ? size_t(2) * mvn::kWave * 16 : 0;
+}
+
+extern "C" int mvn_v2v_conv3(const void* x, int cin, const void* weight_packed, const float* scale,
+                             const float* shift, int skip_mode, const void* skip, int skip_cin,
+                             const void* skip_weight_packed, const float* skip_scale, const float* skip_shift,
+                             void* out, int B, int V, void* stream) {
+  using namespace mvn;
+  const int rc = check_conv3(x, cin, weight_packed, scale, shift, skip_mode, skip, skip_cin, skip_weight_packed,
+                             skip_scale, skip_shift, out, B, V);
+  if (rc != MVN_OK) return rc;
+  return run_conv3(x, cin, weight_packed, scale, shift, skip_mode, skip, skip_weight_packed, skip_scale, skip_shift,
+                   out, B, V, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t mvn_v2v_res3d_workspace_bytes(int group_frames, int V) {
+  using namespace mvn;
+  if (!volume_ok(V)) return 0;
+  const int G = group_frames > 0 ? group_frames : default_group(V);
+  return size_t(G) * size_t(V) * V * V * CO * 2;
+}
+
+extern "C" int mvn_v2v_res3d(const void* x, int cin, const void* weight1_packed, const float* scale1,
+                             const float* shift1, const void* weight2_packed, const float* scale2,
+                             const float* shift2, int skip_mode, const void* skip_weight_packed,
+                             const float* skip_scale, const float* skip_shift, void* out, void* workspace,
+                             size_t workspace_bytes, int group_frames, int B, int V, void* stream) {
+  using namespace mvn;
+  if (!weight2_packed || !scale2 || !shift2) return MVN_ERR_ARG;
+  if (skip_mode != MVN_SKIP_IDENTITY && skip_mode != MVN_SKIP_POINTWISE) return MVN_ERR_ARG;
+  // conv2 reads the block's input as its skip; conv1's checks cover x, cin, B and V
+  int rc = check_conv3(x, cin, weight1_packed, scale1, shift1, skip_mode, x, cin, skip_weight_packed, skip_scale,
+                       skip_shift, out, B, V);
+  if (rc != MVN_OK) return rc;
+  const int G = group_frames > 0 ? group_frames : default_group(V);
+  if (!workspace || workspace_bytes < mvn_v2v_res3d_workspace_bytes(G, V)) return MVN_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t nvox = size_t(V) * V * V;
+  for (int g = 0; g < B; g += G) {
+    const int n = B - g < G ? B - g : G;
+    const char* xg = static_cast<const char*>(x) + size_t(g) * nvox * cin * 2;
+    rc = run_conv3(xg, cin, weight1_packed, scale1, shift1, MVN_SKIP_NONE, nullptr, nullptr, nullptr, nullptr,
+                   workspace, n, V, st);
+    if (rc != MVN_OK) return rc;
+    rc = run_conv3(workspace, CO, weight2_packed, scale2, shift2, skip_mode, xg, skip_weight_packed, skip_scale,
+                   skip_shift, static_cast<char*>(out) + size_t(g) * nvox * CO * 2, n, V, st);
+    if (rc != MVN_OK) return rc;
+  }
+  return MVN_OK;
+}

@@ -21,6 +21,7 @@ MVN_DTYPE_BF16 = 1
 MVN_AGG_SUM, MVN_AGG_MAX, MVN_AGG_SOFTMAX, MVN_AGG_CONF = 0, 1, 2, 3
 MVN_LAYOUT_NCDHW, MVN_LAYOUT_NDHWC = 0, 1
 MVN_PRECISION_EXACT, MVN_PRECISION_FAST = 0, 1
+MVN_SKIP_NONE, MVN_SKIP_IDENTITY, MVN_SKIP_POINTWISE = 0, 1, 2
 
 _c_int, _c_void_p, _c_float, _c_i64, _c_size_t = (
     ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t)
@@ -65,6 +66,13 @@ SIGNATURES = {
     "mvn_v2v_head_softargmax": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                          _c_void_p, _c_int, _c_float, _c_int, _c_void_p, _c_void_p, _c_int,
                                          _c_void_p, _c_size_t, _c_int] + [_c_int] * 5 + [_c_void_p]),
+    "mvn_v2v_conv3_packed_weight_bytes": (_c_size_t, [_c_int]),
+    "mvn_v2v_conv3_skip_packed_weight_bytes": (_c_size_t, [_c_int]),
+    "mvn_v2v_conv3": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int]
+                      + [_c_void_p] * 4 + [_c_int, _c_int, _c_void_p]),
+    "mvn_v2v_res3d_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
+    "mvn_v2v_res3d": (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 6 + [_c_int] + [_c_void_p] * 5
+                      + [_c_size_t, _c_int, _c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
                                         _c_void_p, _c_void_p] + [_c_int] * 8 + [_c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward_workspace_bytes": (_c_size_t, [_c_int] * 5),

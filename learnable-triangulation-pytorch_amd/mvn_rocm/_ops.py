@@ -271,6 +271,59 @@ def _(x, packed, scale_shift, bias3, coords, cuboids, transfer, softmax, multipl
     return x.new_empty((B, J, 3), dtype=torch.float32), x.new_empty(shape, dtype=_CODE_DTYPE[out_dtype])
 
 
+# --------------------------------------------------------------------------- V2V Res3DBlock
+@_op("v2v_conv3")
+def v2v_conv3(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip_mode: int, skip: Optional[Tensor],
+              skip_packed: Optional[Tensor], skip_scale: Optional[Tensor], skip_shift: Optional[Tensor]) -> Tensor:
+    """x (B,V,V,V,cin) bf16, cin 16 | 32 -> (B,V,V,V,32) bf16: relu(bn(conv3d_3(x)) + skip term)
+    (csrc/v2v_res3d.hip); skip (B,V,V,V,32) with MVN_SKIP_IDENTITY, (B,V,V,V,16) and its packed
+    1x1x1 weights, scale and shift with MVN_SKIP_POINTWISE."""
+    _require_gpu(x, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
+    B, V, cin = x.shape[0], x.shape[1], x.shape[4]
+    out = torch.empty((B, V, V, V, 32), dtype=torch.bfloat16, device=x.device)
+    if out.numel() == 0:                  # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_v2v_conv3(
+        x.data_ptr(), cin, packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(skip_mode), _ptr(skip),
+        skip.shape[4] if skip is not None else 0, _ptr(skip_packed), _ptr(skip_scale), _ptr(skip_shift),
+        out.data_ptr(), B, V, _stream(x))
+    _lib.check(code, "mvn_v2v_conv3")
+    return out
+
+
+@v2v_conv3.register_fake
+def _(x, packed, scale, shift, skip_mode, skip, skip_packed, skip_scale, skip_shift):
+    return x.new_empty((*x.shape[:4], 32), dtype=torch.bfloat16)
+
+
+@_op("v2v_res3d")
+def v2v_res3d(x: Tensor, packed1: Tensor, scale1: Tensor, shift1: Tensor, packed2: Tensor, scale2: Tensor,
+              shift2: Tensor, skip_packed: Optional[Tensor], skip_scale: Optional[Tensor],
+              skip_shift: Optional[Tensor], group_frames: int) -> Tensor:
+    """A whole Res3DBlock in one C call (mvn_v2v_res3d): x (B,V,V,V,cin) bf16 -> (B,V,V,V,32) bf16;
+    the identity skip (cin 32) without skip_packed, the pointwise one (cin 16) with it."""
+    _require_gpu(x, packed1, scale1, shift1, packed2, scale2, shift2, skip_packed, skip_scale, skip_shift)
+    B, V, cin = x.shape[0], x.shape[1], x.shape[4]
+    out = torch.empty((B, V, V, V, 32), dtype=torch.bfloat16, device=x.device)
+    if out.numel() == 0:
+        return out
+    lib = _lib.load()
+    ws_bytes = lib.mvn_v2v_res3d_workspace_bytes(int(group_frames), V)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    mode = _lib.MVN_SKIP_IDENTITY if skip_packed is None else _lib.MVN_SKIP_POINTWISE
+    code = lib.mvn_v2v_res3d(
+        x.data_ptr(), cin, packed1.data_ptr(), scale1.data_ptr(), shift1.data_ptr(), packed2.data_ptr(),
+        scale2.data_ptr(), shift2.data_ptr(), mode, _ptr(skip_packed), _ptr(skip_scale), _ptr(skip_shift),
+        out.data_ptr(), ws.data_ptr(), ws.numel(), int(group_frames), B, V, _stream(x))
+    _lib.check(code, "mvn_v2v_res3d")
+    return out
+
+
+@v2v_res3d.register_fake
+def _(x, packed1, scale1, shift1, packed2, scale2, shift2, skip_packed, skip_scale, skip_shift, group_frames):
+    return x.new_empty((*x.shape[:4], 32), dtype=torch.bfloat16)
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,

@@ -11,8 +11,15 @@ config 5 is two launches and one (B, V^3, 32) bf16 intermediate.
 The other end of the V2V, its pointwise tail ``back_layers[1]``, ``back_layers[2]`` and
 ``output_layer`` (v2v.py:154-160), is ``v2v_head`` / ``V2VHead`` below (csrc/v2v_head.hip,
 DESIGN.md §4.11), alone or in one call with the 3D soft-argmax behind it.
+
+Between them, the five ``Res3DBlock``s that run at the full resolution (``front_layers[1..3]``,
+``encoder_decoder.skip_res1``, ``back_layers[0]``; v2v.py:20-42) are ``v2v_conv3`` /
+``res3d_block`` / ``Res3DBlockCL`` (csrc/v2v_res3d.hip), and ``V2VEval`` is the
+whole eval-mode V2V with the soft-argmax, the pooled interior alone left to torch.
 """
 from __future__ import annotations
+
+from typing import NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -357,6 +364,11 @@ class V2VHead(nn.Module):
         return v2v_head_softargmax(x, self.packed, self.scale_shift, self.bias3, coord_volumes, softmax=softmax,
                                    multiplier=multiplier)
 
+    def forward_channels_last(self, x_cl, coord_volumes, multiplier=1.0, softmax=True):
+        """``forward`` for a (B, Vx, Vy, Vz, 32) bf16 channels-last x."""
+        return v2v_head_softargmax(x_cl, self.packed, self.scale_shift, self.bias3, coord_volumes, softmax=softmax,
+                                   multiplier=multiplier, channels_last=True)
+
 
 def v2v_trunk(v2v_model, x):
     """V2VModel.forward (v2v.py:164-169) up to the head: front_layers, encoder_decoder and
@@ -364,3 +376,271 @@ def v2v_trunk(v2v_model, x):
     x = v2v_model.front_layers(x)
     x = v2v_model.encoder_decoder(x)
     return v2v_model.back_layers[0](x)
+
+
+# --------------------------------------------------------------------------- full-resolution Res3DBlocks
+# Res3DBlock (mvn/models/v2v.py:20-42) at the full resolution — front_layers[1..3],
+# encoder_decoder.skip_res1, back_layers[0] — as two launches of one 3x3x3 MFMA kernel
+# (csrc/v2v_res3d.hip) on channels-last bf16 volumes.
+RES_C = 32
+SKIP_NONE, SKIP_IDENTITY, SKIP_POINTWISE = _lib.MVN_SKIP_NONE, _lib.MVN_SKIP_IDENTITY, _lib.MVN_SKIP_POINTWISE
+
+
+class Res3DParams(NamedTuple):
+    """What ``fold_res3d_block`` returns: the packed bf16 weights and f32 scale / shift of the two
+    3x3x3 convs and, for a block with a 1x1x1 ``skip_con``, of the skip (else None: identity)."""
+    packed1: torch.Tensor
+    scale1: torch.Tensor
+    shift1: torch.Tensor
+    packed2: torch.Tensor
+    scale2: torch.Tensor
+    shift2: torch.Tensor
+    skip_packed: Optional[torch.Tensor] = None
+    skip_scale: Optional[torch.Tensor] = None
+    skip_shift: Optional[torch.Tensor] = None
+
+
+def _mfma_a_rows():
+    lane = torch.arange(64)
+    return lane % 16, (lane // 16).view(64, 1) * 8 + torch.arange(8).view(1, 8)      # row [lane], K-slot [lane][j]
+
+
+def pack_conv3_weight(w):
+    """(32, cin, 3, 3, 3) float64 -> (27, 2, 64, 8) bf16 as mvn_v2v_conv3 reads it:
+    [tap = (dx*3 + dy)*3 + dz][m][lane][j] = w[16 m + (lane & 15)][8 (lane >> 4) + j][dx][dy][dz],
+    zero where 8 (lane >> 4) + j >= cin (cin = 16: K zero-padded)."""
+    cin = w.shape[1]
+    wt = torch.zeros(27, RES_C, 32, dtype=torch.float64)
+    wt[:, :, :cin] = w.reshape(RES_C, cin, 27).permute(2, 0, 1)                     # [tap][cout][cin]
+    row, k = _mfma_a_rows()
+    packed = torch.stack([wt[:, (16 * m + row).view(64, 1).expand(64, 8), k] for m in range(2)], dim=1)
+    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+
+
+def pack_pointwise_skip_weight(w):
+    """(32, 16) float64 -> (2, 64, 8) bf16: [m][lane][j] = w[16 m + (lane & 15)][8 (lane >> 4) + j],
+    zero where 8 (lane >> 4) + j >= 16."""
+    wt = torch.zeros(RES_C, 32, dtype=torch.float64)
+    wt[:, :w.shape[1]] = w
+    row, k = _mfma_a_rows()
+    packed = torch.stack([wt[(16 * m + row).view(64, 1).expand(64, 8), k] for m in range(2)])
+    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+
+
+def _fold_conv_bn(conv, bn, what, ks):
+    """(f64 weight, f64 scale, f64 shift) of an eval-mode Conv3d(16 | 32 -> 32, ks) + BatchNorm3d(32)."""
+    w = conv.weight.detach().to(torch.float64).cpu()
+    if w.dim() != 5 or w.shape[0] != RES_C or w.shape[1] not in (16, 32) or tuple(w.shape[2:]) != (ks,) * 3:
+        raise RuntimeError(f"{what}: expected a ({RES_C}, 16 | 32, {ks}, {ks}, {ks}) Conv3d weight, got {tuple(w.shape)}")
+    pad = (ks - 1) // 2
+    if tuple(conv.stride) != (1, 1, 1) or tuple(conv.padding) != (pad,) * 3 or tuple(conv.dilation) != (1, 1, 1):
+        raise RuntimeError(f"{what}: expected stride 1, padding {pad} and no dilation")
+    if bn.running_mean is None or tuple(bn.running_mean.shape) != (RES_C,):
+        raise RuntimeError(f"{what}: expected a BatchNorm3d({RES_C}) with running statistics")
+    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(RES_C, dtype=torch.float64)
+    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
+    return w, s, shift
+
+
+def fold_res3d_block(block, device="cuda"):
+    """An eval-mode module with Res3DBlock's attributes (``res_branch[0..4]`` = conv, BN, ReLU,
+    conv, BN; ``skip_con`` empty or [conv 1x1x1, BN]) with 16 | 32 -> 32 channels -> ``Res3DParams``
+    on ``device``.  BN and the conv biases are folded in float64 as in ``fold_basic3d_block``; the
+    weights are rounded to bf16 and packed as mvn_v2v_conv3 expects (``pack_conv3_weight``)."""
+    rb, sk = block.res_branch, block.skip_con
+    if len(rb) != 5 or len(sk) not in (0, 2):
+        raise RuntimeError(f"expected res_branch of 5 modules and skip_con of 0 or 2, got {len(rb)} and {len(sk)}")
+    w1, s1, t1 = _fold_conv_bn(rb[0], rb[1], "res_branch[0]", 3)
+    w2, s2, t2 = _fold_conv_bn(rb[3], rb[4], "res_branch[3]", 3)
+    cin = w1.shape[1]
+    if w2.shape[1] != RES_C:
+        raise RuntimeError(f"res_branch[3]: expected {RES_C} input channels, got {w2.shape[1]}")
+    dev = torch.device(device)
+    skip = (None, None, None)
+    if len(sk) == 2:
+        ws, ss, ts = _fold_conv_bn(sk[0], sk[1], "skip_con[0]", 1)
+        if cin != 16 or ws.shape[1] != 16:
+            raise RuntimeError(f"a block with a 1x1x1 skip_con must take 16 channels, got {cin} and {ws.shape[1]}")
+        skip = (pack_pointwise_skip_weight(ws.reshape(RES_C, 16)).to(dev), ss.float().to(dev), ts.float().to(dev))
+    elif cin != RES_C:
+        raise RuntimeError(f"a block with an empty skip_con must take {RES_C} channels, got {cin}")
+    return Res3DParams(pack_conv3_weight(w1).to(dev), s1.float().to(dev), t1.float().to(dev),
+                       pack_conv3_weight(w2).to(dev), s2.float().to(dev), t2.float().to(dev), *skip)
+
+
+def _res_volume(what, x, name="x_cl", channels=(16, 32)):
+    """Checked contiguous (B, V, V, V, C) bf16 volume of the Res3DBlock kernel."""
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"{what}: {name} must be bfloat16, got {x.dtype}")
+    if x.dim() != 5 or x.shape[4] not in channels or len(set(x.shape[1:4])) != 1:
+        raise RuntimeError(f"{what}: {name} must be (B, V, V, V, {' | '.join(map(str, channels))}), got {tuple(x.shape)}")
+    V = x.shape[1]
+    if V % 16 != 0 or not 16 <= V <= 256:
+        raise RuntimeError(f"{what}: V must be a multiple of 16 in [16, 256], got {V}")
+    return x.contiguous()
+
+
+def _res_conv_params(what, packed, scale, shift, shape=(27, 2, 64, 8)):
+    if (tuple(packed.shape) != shape or packed.dtype != torch.bfloat16
+            or any(tuple(t.shape) != (RES_C,) or t.dtype != torch.float32 for t in (scale, shift))):
+        raise RuntimeError(f"{what}: packed weights, scale and shift must be what fold_res3d_block returns")
+    return packed.contiguous(), scale.contiguous(), shift.contiguous()
+
+
+def v2v_conv3(x_cl, packed, scale, shift, skip=None, skip_packed=None, skip_scale=None, skip_shift=None):
+    """(B, V, V, V, 16 | 32) bf16 channels-last -> (B, V, V, V, 32) bf16: one launch of
+    relu(bn(conv3d_3(x)) + skip term) (mvn_v2v_conv3, eval mode).  Without ``skip`` there is no
+    residual; ``skip`` (B, V, V, V, 32) alone is added as it is (identity); ``skip`` (B, V, V, V, 16)
+    with ``skip_packed``, ``skip_scale``, ``skip_shift`` goes through its folded 1x1x1 conv + BN.
+    V is a multiple of 16 in [16, 256].  Non-finite voxels follow torch (mvn_hip.h).
+    Inference-only."""
+    from . import _ops
+    what = "v2v_conv3"
+    _inference_only(what, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift,
+                    instead="the model's own Res3DBlock, which autograd records")
+    x = _res_volume(what, x_cl)
+    packed, scale, shift = _res_conv_params(what, packed, scale, shift)
+    pw = (skip_packed, skip_scale, skip_shift)
+    if skip is None:
+        if any(t is not None for t in pw):
+            raise RuntimeError(f"{what}: skip weights without a skip volume")
+        mode = SKIP_NONE
+    else:
+        mode = SKIP_POINTWISE if skip_packed is not None else SKIP_IDENTITY
+        skip = _res_volume(what, skip, "skip", (16,) if mode == SKIP_POINTWISE else (32,))
+        if tuple(skip.shape[:4]) != tuple(x.shape[:4]):
+            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)}")
+        if mode == SKIP_POINTWISE:
+            if skip_scale is None or skip_shift is None:
+                raise RuntimeError(f"{what}: a pointwise skip needs skip_packed, skip_scale and skip_shift")
+            pw = _res_conv_params(what, skip_packed, skip_scale, skip_shift, (2, 64, 8))
+        elif any(t is not None for t in pw):
+            raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
+    return _ops.call(_ops.v2v_conv3, x, packed, scale, shift, mode, skip, *pw)
+
+
+def res3d_block(x_cl, params, group_frames=0):
+    """A whole eval-mode Res3DBlock (v2v.py:20-42) in one call (``mvn_v2v_res3d``): x_cl
+    (B, V, V, V, 16 | 32) bf16 channels-last -> (B, V, V, V, 32) bf16, ``params`` from
+    ``fold_res3d_block``.  conv1 writes one frame group's hidden volume into a workspace
+    (``group_frames`` <= 0: the default, within half of the MALL, 8 frames at V = 64), conv2 reads
+    it with the block's input as its skip.  Equal bit for bit to the two ``v2v_conv3`` launches on
+    the whole batch.  Inference-only."""
+    from . import _ops
+    what = "res3d_block"
+    p = Res3DParams(*params)
+    _inference_only(what, x_cl, *p, instead="the model's own Res3DBlock, which autograd records")
+    pointwise = p.skip_packed is not None
+    x = _res_volume(what, x_cl, channels=(16,) if pointwise else (32,))
+    c1 = _res_conv_params(what, p.packed1, p.scale1, p.shift1)
+    c2 = _res_conv_params(what, p.packed2, p.scale2, p.shift2)
+    if pointwise:
+        if p.skip_scale is None or p.skip_shift is None:
+            raise RuntimeError(f"{what}: a pointwise skip needs skip_packed, skip_scale and skip_shift")
+        sk = _res_conv_params(what, p.skip_packed, p.skip_scale, p.skip_shift, (2, 64, 8))
+    else:
+        sk = (None, None, None)
+    return _ops.call(_ops.v2v_res3d, x, *c1, *c2, *sk, int(group_frames))
+
+
+class Res3DBlockCL(nn.Module):
+    """Eval-mode replacement of a full-resolution Res3DBlock(16 | 32, 32) on a channels-last bf16
+    volume: ``Res3DBlockCL.from_reference(block)(x_cl)``."""
+
+    def __init__(self, params):
+        super().__init__()
+        for name, t in zip(Res3DParams._fields, Res3DParams(*params)):
+            self.register_buffer(name, t)
+
+    @classmethod
+    def from_reference(cls, block, device="cuda"):
+        return cls(fold_res3d_block(block, device=device))
+
+    @property
+    def params(self):
+        return Res3DParams(*(getattr(self, name) for name in Res3DParams._fields))
+
+    def forward(self, x_cl, group_frames=0):
+        return res3d_block(x_cl, self.params, group_frames)
+
+
+def v2v_interior(encoder_decoder, x):
+    """The pooled part of EncoderDecorder.forward (v2v.py:105-135): everything between skip_res1
+    and the last ``+ skip_x1``, 32^3 and below at V = 64, with the model's own modules."""
+    ed = encoder_decoder
+    x = ed.encoder_res1(ed.encoder_pool1(x))
+    s2 = ed.skip_res2(x)
+    x = ed.encoder_res2(ed.encoder_pool2(x))
+    s3 = ed.skip_res3(x)
+    x = ed.encoder_res3(ed.encoder_pool3(x))
+    s4 = ed.skip_res4(x)
+    x = ed.encoder_res4(ed.encoder_pool4(x))
+    s5 = ed.skip_res5(x)
+    x = ed.encoder_res5(ed.encoder_pool5(x))
+    x = ed.mid_res(x)
+    x = ed.decoder_upsample5(ed.decoder_res5(x)) + s5
+    x = ed.decoder_upsample4(ed.decoder_res4(x)) + s4
+    x = ed.decoder_upsample3(ed.decoder_res3(x)) + s3
+    x = ed.decoder_upsample2(ed.decoder_res2(x)) + s2
+    return ed.decoder_upsample1(ed.decoder_res1(x))
+
+
+class V2VEval(nn.Module):
+    """The whole eval-mode V2VModel (v2v.py:141-169) with the 3D soft-argmax behind it, every
+    full-resolution layer on this package's kernels: ``V2VEval.from_reference(m)(vol_cl,
+    coord_volumes, volume_multiplier)`` replaces triangulation.py:352-353 for the channels-last
+    bf16 volume of ``unproject_channels_last``.  Data flow and what each torch glue step costs
+    per frame at V = 64:
+
+    1. ``v2v_front`` with bf16 output (B, 16, V, V, V), then one torch permute to channels-last:
+       an extra read and write of the 16-channel volume (2 x 8.4 MB);
+    2. ``front_layers[1..3]`` and ``encoder_decoder.skip_res1``: ``res3d_block`` (this kernel);
+    3. the pooled interior (``encoder_pool1`` ... ``decoder_upsample1``, 32^3 and below) with the
+       model's own torch modules in ``interior_dtype`` on an NCDHW view of the channels-last
+       volume: the cast reads 16.8 MB of bf16 and writes the volume in ``interior_dtype``, and
+       the modules make whatever layout copies their backend wants;
+    4. ``+ skip_x1`` in ``interior_dtype`` and the cast back to channels-last bf16: two more
+       passes over a 32-channel volume (read 33.6 MB + 16.8 MB, write 33.6 MB; read 33.6 MB,
+       write 16.8 MB, for float32);
+    5. ``back_layers[0]``: ``res3d_block``;
+    6. ``v2v_head_softargmax(channels_last=True)``.
+
+    The interior modules are a copy of the model's (its parameters frozen), so later changes to
+    the model do not reach this module.  Inference-only."""
+
+    def __init__(self, front, front_res, skip_res1, interior, back_res, head, interior_dtype=torch.float32):
+        super().__init__()
+        self.front, self.front_res, self.skip_res1 = front, nn.ModuleList(front_res), skip_res1
+        self.interior, self.back_res, self.head = interior, back_res, head
+        self.interior_dtype = interior_dtype
+
+    @classmethod
+    def from_reference(cls, v2v_model, interior_dtype=torch.float32, device="cuda"):
+        import copy
+        fl, ed = v2v_model.front_layers, v2v_model.encoder_decoder
+        if len(fl) != 4:
+            raise RuntimeError(f"expected front_layers of 4 modules, got {len(fl)}")
+        interior = copy.deepcopy(ed).eval().to(device=device, dtype=interior_dtype).requires_grad_(False)
+        del interior.skip_res1                              # runs on the kernel
+        return cls(Basic3DBlockFront.from_reference(fl[0], device=device),
+                   [Res3DBlockCL.from_reference(fl[i], device=device) for i in (1, 2, 3)],
+                   Res3DBlockCL.from_reference(ed.skip_res1, device=device), interior,
+                   Res3DBlockCL.from_reference(v2v_model.back_layers[0], device=device),
+                   V2VHead.from_reference(v2v_model, device=device), interior_dtype)
+
+    def trunk(self, vol_cl):
+        """(B, V, V, V, 32) bf16 unprojected volume -> the (B, V, V, V, 32) bf16 input of the head."""
+        _inference_only("V2VEval", vol_cl, instead="the model's own modules, which autograd records")
+        h = self.front(vol_cl, torch.bfloat16).permute(0, 2, 3, 4, 1).contiguous()
+        for blk in self.front_res:
+            h = blk(h)
+        skip_x1 = self.skip_res1(h)
+        x = v2v_interior(self.interior, h.permute(0, 4, 1, 2, 3).to(self.interior_dtype))
+        x = x + skip_x1.permute(0, 4, 1, 2, 3)
+        return self.back_res(x.permute(0, 2, 3, 4, 1).to(torch.bfloat16).contiguous())
+
+    def forward(self, vol_cl, coord_volumes, multiplier=1.0, softmax=True):
+        """(keypoints (B, J, 3), volumes (B, J, V, V, V)) as ``op.integrate_tensor_3d_with_coordinates``
+        of the model's output times ``multiplier``."""
+        return self.head.forward_channels_last(self.trunk(vol_cl), coord_volumes, multiplier, softmax)
