@@ -617,6 +617,18 @@ int mvn_debug_x4_block_tiles(int order, int frames, int nTx, int nTy, int nTz, i
  */
 int mvn_debug_x4_image_slots(int shape);
 
+/*
+ * Diagnostics (tests): mvn_dlt with a trace of its null-vector solver (csrc/dlt_solver.hpp).
+ * The same per-point code, so out_xyz (B, J, 3) holds mvn_dlt's bits; per point (B, J, int32)
+ *   path   0 = an exactly zero column of R, 1 = inverse iteration, 2 = the Jacobi SVD
+ *   steps  the inverse-iteration steps run (path 1), the Jacobi sweeps run, the last,
+ *          rotation-free one included (path 2), 0 (path 0).
+ * conf may be null (all ones).  Returns MVN_OK, MVN_ERR_ARG for a null pointer, MVN_ERR_SHAPE
+ * as mvn_dlt, MVN_ERR_LAUNCH.
+ */
+int mvn_debug_dlt_trace(const float* proj, const float* pts, const float* conf, float* out_xyz,
+                        int* path, int* steps, int B, int N, int J, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

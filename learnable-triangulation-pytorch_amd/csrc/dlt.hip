@@ -11,8 +11,9 @@
 //      Newton-refined hardware reciprocal square roots: round 3, config 1 latency),
 //      so R^T R = A^T A without ever squaring the condition number and for any N,
 //   3. the right singular vector of the smallest singular value is the homogeneous point
-//      (multiview.py:154-156): inverse iteration on R^T R (2-3 steps), or, when that does
-//      not converge (near-equal smallest singular values), a one-sided Jacobi SVD of R (f64),
+//      (multiview.py:154-156): inverse iteration on R^T R (4-6 steps), or, when that does
+//      not converge (near-equal smallest singular values) or settles on another singular
+//      vector (a null vector orthogonal to its start), a one-sided Jacobi SVD of R (f64),
 //   4. X[:3] / X[3] (multiview.py:157; sign of the null vector cancels).
 #include "common.hpp"
 #include "dlt_solver.hpp"
@@ -37,6 +38,27 @@ __global__ __launch_bounds__(kDltBlock) void dlt_kernel(const float* __restrict_
   o[2] = x[2];
 }
 
+// dlt_kernel with the solver's trace parameter on (mvn_debug_dlt_trace): the same dlt_point, so
+// the same bits in out, plus the path taken and its step count per point.
+__global__ __launch_bounds__(kDltBlock) void dlt_trace_kernel(const float* __restrict__ P, const float* __restrict__ pts,
+                                                              const float* __restrict__ conf, float* __restrict__ out,
+                                                              int* __restrict__ path, int* __restrict__ steps, int B,
+                                                              int N, int J) {
+  const int t = blockIdx.x * kDltBlock + threadIdx.x;
+  if (t >= B * J) return;
+  const int b = t / J, j = t - b * J;
+
+  float x[3];
+  int pa = 0, st = 0;
+  dlt_point<true>(P, pts, conf, b, j, N, J, x, &pa, &st);
+  float* o = out + size_t(t) * 3;
+  o[0] = x[0];
+  o[1] = x[1];
+  o[2] = x[2];
+  path[t] = pa;
+  steps[t] = st;
+}
+
 }  // namespace
 }  // namespace mvn
 
@@ -48,6 +70,18 @@ extern "C" int mvn_dlt(const float* proj, const float* pts, const float* conf, f
   if ((long long)B * J > (1LL << 30)) return MVN_ERR_SHAPE;
   const int n = B * J;
   dlt_kernel<<<(n + kDltBlock - 1) / kDltBlock, kDltBlock, 0, static_cast<hipStream_t>(stream)>>>(proj, pts, conf, out, B, N, J);
+  return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
+}
+
+extern "C" int mvn_debug_dlt_trace(const float* proj, const float* pts, const float* conf, float* out_xyz, int* path,
+                                   int* steps, int B, int N, int J, void* stream) {
+  using namespace mvn;
+  if (!proj || !pts || !out_xyz || !path || !steps) return MVN_ERR_ARG;
+  if (B <= 0 || N <= 0 || J <= 0) return MVN_ERR_SHAPE;
+  if ((long long)B * J > (1LL << 30)) return MVN_ERR_SHAPE;
+  const int n = B * J;
+  dlt_trace_kernel<<<(n + kDltBlock - 1) / kDltBlock, kDltBlock, 0, static_cast<hipStream_t>(stream)>>>(
+      proj, pts, conf, out_xyz, path, steps, B, N, J);
   return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
 }
 

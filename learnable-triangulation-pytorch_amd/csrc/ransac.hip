@@ -45,38 +45,11 @@ __device__ __forceinline__ void fold_view(double (&R)[4][4], const float* __rest
   }
 }
 
-// Null vector of R as dlt_kernel takes it (exact zero column, inverse iteration, Jacobi SVD),
-// dehomogenised (multiview.py:125-127).
+// Null vector of R as dlt_kernel takes it (dlt_solver.hpp null_vector: exact zero column, inverse
+// iteration, Jacobi SVD), dehomogenised (multiview.py:125-127).
 __device__ __forceinline__ void solve_point(double (&R)[4][4], double (&x)[3]) {
-  int zcol = -1;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    bool z = true;
-#pragma unroll
-    for (int i = 0; i <= k; ++i) z &= R[i][k] == 0.0;
-    if (z) zcol = k;
-  }
   double X[4];
-  if (zcol >= 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) X[i] = i == zcol ? 1.0 : 0.0;
-  } else if (!inverse_iteration(R, X)) {
-    double V[4][4];
-    jacobi_svd(R, V);
-    int kmin = 0;
-    double smin = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const double n2 = R[0][k] * R[0][k] + R[1][k] * R[1][k] + R[2][k] * R[2][k] + R[3][k] * R[3][k];
-      if (k == 0 || n2 <= smin) { smin = n2; kmin = k; }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      X[i] = V[i][0];
-#pragma unroll
-      for (int k = 1; k < 4; ++k) if (kmin == k) X[i] = V[i][k];
-    }
-  }
+  null_vector(R, X);
 #pragma unroll
   for (int i = 0; i < 3; ++i) x[i] = X[i] / X[3];
 }

@@ -96,6 +96,7 @@ SIGNATURES = {
     "mvn_debug_unproject_occupancy": (_c_int, [_c_int]),
     "mvn_debug_x4_block_tiles": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_int)]),
     "mvn_debug_x4_image_slots": (_c_int, [_c_int]),
+    "mvn_debug_dlt_trace": (_c_int, [_c_void_p] * 6 + [_c_int, _c_int, _c_int, _c_void_p]),
 }
 
 _lib = None

@@ -148,6 +148,16 @@ def test_dlt_argument_validation(lib):
     assert lib.mvn_dlt(1, 1, None, 1, 1, 0, 17, None) == -2
 
 
+def test_dlt_trace_argument_validation(lib):
+    """mvn_debug_dlt_trace checks as mvn_dlt does, and its two trace outputs, before any HIP call."""
+    def call(ptrs=(1, 1, None, 1, 1, 1), B=1, N=4, J=17):
+        return lib.mvn_debug_dlt_trace(*ptrs, B, N, J, None)
+    for i in (0, 1, 3, 4, 5):                            # proj, pts, out_xyz, path, steps (conf may be null)
+        assert call(ptrs=tuple(None if j == i else (None if j == 2 else 1) for j in range(6))) == -1, i
+    for bad in (dict(B=0), dict(N=0), dict(J=-1), dict(B=1 << 16, J=1 << 15)):
+        assert call(**bad) == -2, bad
+
+
 def test_python_api_has_no_cpu_fallback():
     from mvn_rocm import op, multiview
     feat = torch.zeros(1, 2, 3, 8, 8)
