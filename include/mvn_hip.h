@@ -28,6 +28,10 @@
  *   mvn_v2v_conv3, mvn_v2v_res3d
  *                        <- mvn/models/v2v.py:20-42 (Res3DBlock at the full resolution:
  *                           front_layers[1..3], skip_res1, back_layers[0]; eval mode)
+ *   mvn_v2v_maxpool2, mvn_v2v_conv3_wide, mvn_v2v_upsample2
+ *                        <- mvn/models/v2v.py:45-65, 105-135 (the encoder-decoder's first pooled
+ *                           level: encoder_pool1, encoder_res1, skip_res2, decoder_res1 and
+ *                           decoder_upsample1 with the last `+ skip_x1`; eval mode)
  *   mvn_triangulate_ransac <-mvn/models/triangulation.py:54-128 (the RANSAC baseline's host
  *                           loop: hypotheses, inlier DLT, Huber refinement)
  *   mvn_reprojection_error <- mvn/utils/multiview.py:177-184 calc_reprojection_error_matrix(...)
@@ -363,6 +367,79 @@ int mvn_v2v_res3d(const void* x, int cin, const void* weight1_packed, const floa
                   const void* weight2_packed, const float* scale2, const float* shift2, int skip_mode,
                   const void* skip_weight_packed, const float* skip_scale, const float* skip_shift, void* out,
                   void* workspace, size_t workspace_bytes, int group_frames, int B, int V, void* stream);
+
+/*
+ * F.max_pool3d(x, 2, 2) on a channels-last bf16 volume (Pool3DBlock(2), v2v.py:45-51), bit for
+ * bit as torch computes it: per output voxel and channel the 8 window values are scanned in the
+ * order x, y, z (z fastest) with m = -inf and the update `v > m || isnan(v)`: a NaN in the window
+ * gives a NaN (the last one's bits), an all-negative window its largest value (never 0), a window
+ * of -inf gives -inf, and among equal maxima (+0 and -0 included) the first in scan order wins.
+ *   x    (B, V, V, V, C) bf16;  V even, 2 <= V <= 256;  C % 8 == 0, 8 <= C <= 128
+ *   out  (B, V/2, V/2, V/2, C) bf16; must not overlap x
+ * MVN_ERR_ARG for a null pointer; MVN_ERR_SHAPE for B < 1 or a V or C outside these sets.
+ * Stream-ordered, allocates nothing, reentrant.
+ */
+int mvn_v2v_maxpool2(const void* x, void* out, int B, int V, int C, void* stream);
+
+/*
+ * mvn_v2v_conv3 with 64 output channels, for the Res3DBlocks of the first pooled level
+ * (Res3DBlock(32, 64) and Res3DBlock(64, 64), v2v.py:20-42): Conv3d(cin -> 64, k = 3, stride 1,
+ * zero padding 1) + BatchNorm3d, an optional residual, ReLU.  The arithmetic per output voxel and
+ * channel is mvn_v2v_conv3's (acc, pre, r, y above), with
+ *   x              (B, V, V, V, cin) bf16, cin 32 | 64;  V % 16 == 0, 16 <= V <= 128
+ *   weight_packed  mvn_v2v_conv3_wide_packed_weight_bytes(cin) = 27 * (cin / 32) * 4 * 64 * 8 * 2
+ *                  bytes: bf16 weights as
+ *                  [tap = (dx*3 + dy)*3 + dz][kp 0..cin/32-1][m 0..3][lane 0..63][j 0..7]
+ *                    = W[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]
+ *                  (W the Conv3d weight (64, cin, 3, 3, 3); tap (dx, dy, dz) multiplies input
+ *                  voxel (x + dx - 1, y + dy - 1, z + dz - 1))
+ *   scale, shift   (64) f32: BN and the conv bias folded
+ *   skip           NONE: NULL.  IDENTITY: (B, V, V, V, 64) bf16, skip_cin 64.  POINTWISE:
+ *                  (B, V, V, V, 32) bf16, skip_cin 32.  Must not overlap out.
+ *   skip_weight_packed  POINTWISE only (NULL otherwise),
+ *                  mvn_v2v_conv3_wide_skip_packed_weight_bytes(32) = 4 * 64 * 8 * 2 bytes:
+ *                  [m 0..3][lane 0..63][j 0..7] = Ws[16 m + (lane & 15)][8 (lane >> 4) + j]
+ *                  (Ws the 1x1x1 Conv3d weight (64, 32))
+ *   skip_scale, skip_shift  POINTWISE only (NULL otherwise): (64) f32
+ *   out            (B, V, V, V, 64) bf16
+ * A NaN or infinite input voxel reaches exactly its clipped 3^3 neighbourhood in all 64
+ * channels, a non-finite skip voxel exactly its own voxel.  Errors as mvn_v2v_conv3:
+ * MVN_ERR_ARG for a null required pointer, an unknown skip_mode or skip pointers that contradict
+ * the mode; MVN_ERR_SHAPE for B < 1, a V outside the multiples of 16 in [16, 128], a cin other
+ * than 32 / 64, a skip_cin other than 64 with IDENTITY or other than 32 with POINTWISE.  The size
+ * functions return 0 for a cin they do not take.  Stream-ordered, allocates nothing, reentrant.
+ */
+size_t mvn_v2v_conv3_wide_packed_weight_bytes(int cin);
+size_t mvn_v2v_conv3_wide_skip_packed_weight_bytes(int cin);
+int mvn_v2v_conv3_wide(const void* x, int cin, const void* weight_packed, const float* scale, const float* shift,
+                       int skip_mode, const void* skip, int skip_cin, const void* skip_weight_packed,
+                       const float* skip_scale, const float* skip_shift, void* out, int B, int V, void* stream);
+
+/*
+ * Upsample3DBlock(64, 32, 2, 2), eval mode (v2v.py:53-65: ConvTranspose3d(64, 32, k = 2, stride 2)
+ * + BatchNorm3d + ReLU), fused with the encoder-decoder's last `+ skip_x1` (v2v.py:133).  Per
+ * input voxel (x, y, z), offset (dx, dy, dz) in {0, 1}^3 and output channel co:
+ *   acc = sum over ci of in[x, y, z][ci] * W[ci][co][dx][dy][dz]   (bf16 operands, f32
+ *         accumulation on MFMA, summation order free)
+ *   pre = fmaf(acc, scale[co], shift[co])
+ *   u   = pre <= 0 ? +0 : pre                                      (a NaN stays NaN)
+ *   out[2x + dx, 2y + dy, 2z + dz][co] = bf16(u + float(skip[...][co])), nearest-even
+ * (the ReLU before the add, none after it; without skip, bf16(u)).
+ *   x              (B, V, V, V, 64) bf16;  V % 16 == 0, 16 <= V <= 128
+ *   weight_packed  mvn_v2v_upsample2_packed_weight_bytes() = 2 * 16 * 64 * 8 * 2 bytes: bf16 as
+ *                  [kp 0..1][m 0..15][lane 0..63][j 0..7]
+ *                    = W[32 kp + 8 (lane >> 4) + j][16 (m & 1) + (lane & 15)][dx][dy][dz],
+ *                  (dx*2 + dy)*2 + dz = m >> 1  (W the ConvTranspose3d weight (64, 32, 2, 2, 2))
+ *   scale, shift   (32) f32: BN and the ConvTranspose bias folded
+ *   skip           (B, 2V, 2V, 2V, 32) bf16, or NULL for no add; must not overlap out
+ *   out            (B, 2V, 2V, 2V, 32) bf16
+ * A non-finite input voxel reaches exactly its own 2x2x2 outputs (all channels), a non-finite
+ * skip voxel exactly itself.  MVN_ERR_ARG for a null required pointer; MVN_ERR_SHAPE for B < 1 or
+ * a V outside the multiples of 16 in [16, 128].  Stream-ordered, allocates nothing, reentrant.
+ */
+size_t mvn_v2v_upsample2_packed_weight_bytes(void);
+int mvn_v2v_upsample2(const void* x, const void* weight_packed, const float* scale, const float* shift,
+                      const void* skip, void* out, int B, int V, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

@@ -73,6 +73,13 @@ SIGNATURES = {
     "mvn_v2v_res3d_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
     "mvn_v2v_res3d": (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 6 + [_c_int] + [_c_void_p] * 5
                       + [_c_size_t, _c_int, _c_int, _c_int, _c_void_p]),
+    "mvn_v2v_maxpool2": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
+    "mvn_v2v_conv3_wide_packed_weight_bytes": (_c_size_t, [_c_int]),
+    "mvn_v2v_conv3_wide_skip_packed_weight_bytes": (_c_size_t, [_c_int]),
+    "mvn_v2v_conv3_wide": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int]
+                           + [_c_void_p] * 4 + [_c_int, _c_int, _c_void_p]),
+    "mvn_v2v_upsample2_packed_weight_bytes": (_c_size_t, []),
+    "mvn_v2v_upsample2": (_c_int, [_c_void_p] * 6 + [_c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
                                         _c_void_p, _c_void_p] + [_c_int] * 8 + [_c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward_workspace_bytes": (_c_size_t, [_c_int] * 5),

@@ -324,6 +324,73 @@ def _(x, packed1, scale1, shift1, packed2, scale2, shift2, skip_packed, skip_sca
     return x.new_empty((*x.shape[:4], 32), dtype=torch.bfloat16)
 
 
+# --------------------------------------------------------------------------- V2V first pooled level
+@_op("v2v_maxpool2")
+def v2v_maxpool2(x: Tensor) -> Tensor:
+    """x (B,V,V,V,C) bf16 -> (B,V/2,V/2,V/2,C) bf16: F.max_pool3d(x, 2, 2) channels-last
+    (csrc/v2v_interior.hip)."""
+    _require_gpu(x)
+    B, V, C = x.shape[0], x.shape[1], x.shape[4]
+    out = torch.empty((B, V // 2, V // 2, V // 2, C), dtype=torch.bfloat16, device=x.device)
+    if out.numel() == 0:                  # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_v2v_maxpool2(x.data_ptr(), out.data_ptr(), B, V, C, _stream(x))
+    _lib.check(code, "mvn_v2v_maxpool2")
+    return out
+
+
+@v2v_maxpool2.register_fake
+def _(x):
+    B, V, C = x.shape[0], x.shape[1], x.shape[4]
+    return x.new_empty((B, V // 2, V // 2, V // 2, C), dtype=torch.bfloat16)
+
+
+@_op("v2v_conv3_wide")
+def v2v_conv3_wide(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip_mode: int, skip: Optional[Tensor],
+                   skip_packed: Optional[Tensor], skip_scale: Optional[Tensor],
+                   skip_shift: Optional[Tensor]) -> Tensor:
+    """x (B,V,V,V,cin) bf16, cin 32 | 64 -> (B,V,V,V,64) bf16: relu(bn(conv3d_3(x)) + skip term)
+    (csrc/v2v_interior.hip); skip (B,V,V,V,64) with MVN_SKIP_IDENTITY, (B,V,V,V,32) and its packed
+    1x1x1 weights, scale and shift with MVN_SKIP_POINTWISE."""
+    _require_gpu(x, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
+    B, V, cin = x.shape[0], x.shape[1], x.shape[4]
+    out = torch.empty((B, V, V, V, 64), dtype=torch.bfloat16, device=x.device)
+    if out.numel() == 0:                  # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_v2v_conv3_wide(
+        x.data_ptr(), cin, packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(skip_mode), _ptr(skip),
+        skip.shape[4] if skip is not None else 0, _ptr(skip_packed), _ptr(skip_scale), _ptr(skip_shift),
+        out.data_ptr(), B, V, _stream(x))
+    _lib.check(code, "mvn_v2v_conv3_wide")
+    return out
+
+
+@v2v_conv3_wide.register_fake
+def _(x, packed, scale, shift, skip_mode, skip, skip_packed, skip_scale, skip_shift):
+    return x.new_empty((*x.shape[:4], 64), dtype=torch.bfloat16)
+
+
+@_op("v2v_upsample2")
+def v2v_upsample2(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip: Optional[Tensor]) -> Tensor:
+    """x (B,V,V,V,64) bf16 -> (B,2V,2V,2V,32) bf16: relu(bn(conv_transpose3d_2(x))) + skip
+    (csrc/v2v_interior.hip); skip (B,2V,2V,2V,32) bf16 or None."""
+    _require_gpu(x, packed, scale, shift, skip)
+    B, V = x.shape[0], x.shape[1]
+    out = torch.empty((B, 2 * V, 2 * V, 2 * V, 32), dtype=torch.bfloat16, device=x.device)
+    if out.numel() == 0:                  # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_v2v_upsample2(x.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                         _ptr(skip), out.data_ptr(), B, V, _stream(x))
+    _lib.check(code, "mvn_v2v_upsample2")
+    return out
+
+
+@v2v_upsample2.register_fake
+def _(x, packed, scale, shift, skip):
+    B, V = x.shape[0], x.shape[1]
+    return x.new_empty((B, 2 * V, 2 * V, 2 * V, 32), dtype=torch.bfloat16)
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,

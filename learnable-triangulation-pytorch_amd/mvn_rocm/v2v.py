@@ -15,7 +15,10 @@ DESIGN.md §4.11), alone or in one call with the 3D soft-argmax behind it.
 Between them, the five ``Res3DBlock``s that run at the full resolution (``front_layers[1..3]``,
 ``encoder_decoder.skip_res1``, ``back_layers[0]``; v2v.py:20-42) are ``v2v_conv3`` /
 ``res3d_block`` / ``Res3DBlockCL`` (csrc/v2v_res3d.hip), and ``V2VEval`` is the
-whole eval-mode V2V with the soft-argmax, the pooled interior alone left to torch.
+whole eval-mode V2V with the soft-argmax, the pooled interior alone left to torch.  With
+``half_res="kernels"`` the interior's first level and its boundaries run on kernels too:
+``max_pool2_cl``, ``v2v_conv3_wide`` / ``res3d_block_wide`` / ``Res3DBlockWideCL`` and
+``upsample2_add`` (csrc/v2v_interior.hip).
 """
 from __future__ import annotations
 
@@ -565,12 +568,271 @@ class Res3DBlockCL(nn.Module):
         return res3d_block(x_cl, self.params, group_frames)
 
 
-def v2v_interior(encoder_decoder, x):
-    """The pooled part of EncoderDecorder.forward (v2v.py:105-135): everything between skip_res1
-    and the last ``+ skip_x1``, 32^3 and below at V = 64, with the model's own modules."""
+# --------------------------------------------------------------------------- first pooled level
+# encoder_pool1, encoder_res1 (Res3DBlock(32, 64)), skip_res2 and decoder_res1 (Res3DBlock(64, 64))
+# and decoder_upsample1 with the last ``+ skip_x1`` (mvn/models/v2v.py:45-65, 105-135) on
+# channels-last bf16 volumes (csrc/v2v_interior.hip).
+WIDE_C = 64
+UP_CIN, UP_COUT = 64, 32
+
+
+def max_pool2_cl(x_cl):
+    """(B, V, V, V, C) bf16 channels-last -> (B, V/2, V/2, V/2, C): ``F.max_pool3d(x, 2, 2)`` bit
+    for bit (mvn_v2v_maxpool2), NaN, infinities and signed zeros included.  V is even in [2, 256],
+    C a multiple of 8 up to 128; a non-contiguous ``x_cl`` is copied.  Inference-only."""
+    from . import _ops
+    what = "max_pool2_cl"
+    _inference_only(what, x_cl, instead="torch.nn.functional.max_pool3d, which autograd records")
+    if x_cl.dtype != torch.bfloat16:
+        raise TypeError(f"{what}: x_cl must be bfloat16, got {x_cl.dtype}")
+    if x_cl.dim() != 5 or len(set(x_cl.shape[1:4])) != 1:
+        raise RuntimeError(f"{what}: x_cl must be (B, V, V, V, C), got {tuple(x_cl.shape)}")
+    V, C = x_cl.shape[1], x_cl.shape[4]
+    if V % 2 != 0 or not 2 <= V <= 256:
+        raise RuntimeError(f"{what}: V must be even in [2, 256], got {V}")
+    if C % 8 != 0 or not 8 <= C <= 128:
+        raise RuntimeError(f"{what}: C must be a multiple of 8 in [8, 128], got {C}")
+    return _ops.call(_ops.v2v_maxpool2, x_cl.contiguous())
+
+
+def pack_conv3_wide_weight(w):
+    """(64, cin, 3, 3, 3) float64, cin 32 | 64 -> (27, cin / 32, 4, 64, 8) bf16 as mvn_v2v_conv3_wide
+    reads it: [tap = (dx*3 + dy)*3 + dz][kp][m][lane][j]
+    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]."""
+    cin = w.shape[1]
+    wt = w.reshape(WIDE_C, cin, 27).permute(2, 0, 1)                                # [tap][cout][cin]
+    row, k = _mfma_a_rows()
+    packed = torch.stack([torch.stack([wt[:, (16 * m + row).view(64, 1).expand(64, 8), 32 * kp + k]
+                                       for m in range(4)], dim=1) for kp in range(cin // 32)], dim=1)
+    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+
+
+def pack_pointwise_skip_wide_weight(w):
+    """(64, 32) float64 -> (4, 64, 8) bf16: [m][lane][j] = w[16 m + (lane & 15)][8 (lane >> 4) + j]."""
+    row, k = _mfma_a_rows()
+    packed = torch.stack([w[(16 * m + row).view(64, 1).expand(64, 8), k] for m in range(4)])
+    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+
+
+def pack_upsample_weight(w):
+    """(64, 32, 2, 2, 2) float64 ConvTranspose3d weight -> (2, 16, 64, 8) bf16 as mvn_v2v_upsample2
+    reads it: [kp][m][lane][j] = w[32 kp + 8 (lane >> 4) + j][16 (m & 1) + (lane & 15)][dx][dy][dz]
+    with (dx*2 + dy)*2 + dz = m >> 1."""
+    wt = w.reshape(UP_CIN, UP_COUT, 8).permute(2, 1, 0)                             # [pos][cout][cin]
+    row, k = _mfma_a_rows()
+    packed = torch.stack([torch.stack([wt[m >> 1][(16 * (m & 1) + row).view(64, 1).expand(64, 8), 32 * kp + k]
+                                       for m in range(16)]) for kp in range(2)])
+    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+
+
+def _fold_conv_bn_wide(conv, bn, what, ks, cins):
+    """(f64 weight, f64 scale, f64 shift) of an eval-mode Conv3d(cins -> 64, ks) + BatchNorm3d(64)."""
+    w = conv.weight.detach().to(torch.float64).cpu()
+    want = " | ".join(map(str, cins))
+    if w.dim() != 5 or w.shape[0] != WIDE_C or w.shape[1] not in cins or tuple(w.shape[2:]) != (ks,) * 3:
+        raise RuntimeError(f"{what}: expected a ({WIDE_C}, {want}, {ks}, {ks}, {ks}) Conv3d weight, got {tuple(w.shape)}")
+    pad = (ks - 1) // 2
+    if tuple(conv.stride) != (1, 1, 1) or tuple(conv.padding) != (pad,) * 3 or tuple(conv.dilation) != (1, 1, 1):
+        raise RuntimeError(f"{what}: expected stride 1, padding {pad} and no dilation")
+    if bn.running_mean is None or tuple(bn.running_mean.shape) != (WIDE_C,):
+        raise RuntimeError(f"{what}: expected a BatchNorm3d({WIDE_C}) with running statistics")
+    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(WIDE_C, dtype=torch.float64)
+    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
+    return w, s, shift
+
+
+def fold_res3d_block_wide(block, device="cuda"):
+    """An eval-mode module with Res3DBlock's attributes and 32 | 64 -> 64 channels (``skip_con``
+    [conv 1x1x1, BN] for 32, empty for 64) -> ``Res3DParams`` on ``device``: folded in float64
+    exactly as ``fold_res3d_block``, packed as mvn_v2v_conv3_wide expects
+    (``pack_conv3_wide_weight``, ``pack_pointwise_skip_wide_weight``)."""
+    rb, sk = block.res_branch, block.skip_con
+    if len(rb) != 5 or len(sk) not in (0, 2):
+        raise RuntimeError(f"expected res_branch of 5 modules and skip_con of 0 or 2, got {len(rb)} and {len(sk)}")
+    w1, s1, t1 = _fold_conv_bn_wide(rb[0], rb[1], "res_branch[0]", 3, (32, 64))
+    w2, s2, t2 = _fold_conv_bn_wide(rb[3], rb[4], "res_branch[3]", 3, (64,))
+    cin = w1.shape[1]
+    dev = torch.device(device)
+    skip = (None, None, None)
+    if len(sk) == 2:
+        ws, ss, ts = _fold_conv_bn_wide(sk[0], sk[1], "skip_con[0]", 1, (32,))
+        if cin != 32:
+            raise RuntimeError(f"a block with a 1x1x1 skip_con must take 32 channels, got {cin}")
+        skip = (pack_pointwise_skip_wide_weight(ws.reshape(WIDE_C, 32)).to(dev), ss.float().to(dev), ts.float().to(dev))
+    elif cin != WIDE_C:
+        raise RuntimeError(f"a block with an empty skip_con must take {WIDE_C} channels, got {cin}")
+    return Res3DParams(pack_conv3_wide_weight(w1).to(dev), s1.float().to(dev), t1.float().to(dev),
+                       pack_conv3_wide_weight(w2).to(dev), s2.float().to(dev), t2.float().to(dev), *skip)
+
+
+class UpsampleParams(NamedTuple):
+    """What ``fold_upsample_block`` returns: packed bf16 weights and f32 scale / shift."""
+    packed: torch.Tensor
+    scale: torch.Tensor
+    shift: torch.Tensor
+
+
+def fold_upsample_block(block, device="cuda"):
+    """An eval-mode module with Upsample3DBlock's attributes (``block[0..2]`` = ConvTranspose3d(64,
+    32, 2, stride 2), BatchNorm3d(32), ReLU) -> ``UpsampleParams`` on ``device``: the ConvTranspose
+    bias and the BN folded in float64, the weights rounded to bf16 and packed as
+    mvn_v2v_upsample2 expects (``pack_upsample_weight``)."""
+    seq = getattr(block, "block", None)
+    if seq is None or len(seq) != 3 or not isinstance(seq[0], nn.ConvTranspose3d):
+        raise RuntimeError("expected block = [ConvTranspose3d, BatchNorm3d, ReLU]")
+    conv, bn = seq[0], seq[1]
+    w = conv.weight.detach().to(torch.float64).cpu()
+    if tuple(w.shape) != (UP_CIN, UP_COUT, 2, 2, 2):
+        raise RuntimeError(f"block[0]: expected a ({UP_CIN}, {UP_COUT}, 2, 2, 2) ConvTranspose3d weight, got {tuple(w.shape)}")
+    if (tuple(conv.stride) != (2, 2, 2) or tuple(conv.padding) != (0, 0, 0) or tuple(conv.output_padding) != (0, 0, 0)
+            or tuple(conv.dilation) != (1, 1, 1) or conv.groups != 1):
+        raise RuntimeError("block[0]: expected stride 2, no padding, no output padding, no dilation, one group")
+    if bn.running_mean is None or tuple(bn.running_mean.shape) != (UP_COUT,):
+        raise RuntimeError(f"block[1]: expected a BatchNorm3d({UP_COUT}) with running statistics")
+    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(UP_COUT, dtype=torch.float64)
+    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
+    dev = torch.device(device)
+    return UpsampleParams(pack_upsample_weight(w).to(dev), s.float().to(dev), shift.float().to(dev))
+
+
+def _wide_volume(what, x, name="x_cl", channels=(32, 64), vmax=128):
+    """Checked contiguous (B, V, V, V, C) bf16 volume of the first pooled level's kernels."""
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"{what}: {name} must be bfloat16, got {x.dtype}")
+    if x.dim() != 5 or x.shape[4] not in channels or len(set(x.shape[1:4])) != 1:
+        raise RuntimeError(f"{what}: {name} must be (B, V, V, V, {' | '.join(map(str, channels))}), got {tuple(x.shape)}")
+    V = x.shape[1]
+    if V % 16 != 0 or not 16 <= V <= vmax:
+        raise RuntimeError(f"{what}: {name}: V must be a multiple of 16 in [16, {vmax}], got {V}")
+    return x.contiguous()
+
+
+def _wide_params(what, packed, scale, shift, shape, channels=WIDE_C):
+    if (tuple(packed.shape) != shape or packed.dtype != torch.bfloat16
+            or any(tuple(t.shape) != (channels,) or t.dtype != torch.float32 for t in (scale, shift))):
+        raise RuntimeError(f"{what}: packed weights {shape}, scale and shift ({channels},) must be what the fold returns")
+    return packed.contiguous(), scale.contiguous(), shift.contiguous()
+
+
+def v2v_conv3_wide(x_cl, packed, scale, shift, skip=None, skip_packed=None, skip_scale=None, skip_shift=None):
+    """(B, V, V, V, 32 | 64) bf16 channels-last -> (B, V, V, V, 64) bf16: one launch of
+    relu(bn(conv3d_3(x)) + skip term) (mvn_v2v_conv3_wide, eval mode).  Without ``skip`` there is
+    no residual; ``skip`` (B, V, V, V, 64) alone is added as it is (identity); ``skip``
+    (B, V, V, V, 32) with ``skip_packed``, ``skip_scale``, ``skip_shift`` goes through its folded
+    1x1x1 conv + BN.  V is a multiple of 16 in [16, 128].  Non-finite voxels follow torch
+    (mvn_hip.h).  Inference-only."""
+    from . import _ops
+    what = "v2v_conv3_wide"
+    _inference_only(what, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift,
+                    instead="the model's own Res3DBlock, which autograd records")
+    x = _wide_volume(what, x_cl)
+    packed, scale, shift = _wide_params(what, packed, scale, shift, (27, x.shape[4] // 32, 4, 64, 8))
+    pw = (skip_packed, skip_scale, skip_shift)
+    if skip is None:
+        if any(t is not None for t in pw):
+            raise RuntimeError(f"{what}: skip weights without a skip volume")
+        mode = SKIP_NONE
+    else:
+        mode = SKIP_POINTWISE if skip_packed is not None else SKIP_IDENTITY
+        skip = _wide_volume(what, skip, "skip", (32,) if mode == SKIP_POINTWISE else (64,))
+        if tuple(skip.shape[:4]) != tuple(x.shape[:4]):
+            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)}")
+        if mode == SKIP_POINTWISE:
+            if skip_scale is None or skip_shift is None:
+                raise RuntimeError(f"{what}: a pointwise skip needs skip_packed, skip_scale and skip_shift")
+            pw = _wide_params(what, skip_packed, skip_scale, skip_shift, (4, 64, 8))
+        elif any(t is not None for t in pw):
+            raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
+    return _ops.call(_ops.v2v_conv3_wide, x, packed, scale, shift, mode, skip, *pw)
+
+
+def res3d_block_wide(x_cl, params):
+    """A whole eval-mode Res3DBlock(32 | 64, 64) as two ``v2v_conv3_wide`` launches: x_cl
+    (B, V, V, V, 32 | 64) bf16 channels-last -> (B, V, V, V, 64) bf16, ``params`` from
+    ``fold_res3d_block_wide``.  The hidden volume is a torch allocation (4.2 MB per frame at 32^3).
+    Inference-only."""
+    what = "res3d_block_wide"
+    p = Res3DParams(*params)
+    _inference_only(what, x_cl, *p, instead="the model's own Res3DBlock, which autograd records")
+    pointwise = p.skip_packed is not None
+    x = _wide_volume(what, x_cl, channels=(32,) if pointwise else (64,))
+    h = v2v_conv3_wide(x, p.packed1, p.scale1, p.shift1)
+    if pointwise:
+        return v2v_conv3_wide(h, p.packed2, p.scale2, p.shift2, x, p.skip_packed, p.skip_scale, p.skip_shift)
+    if p.skip_scale is not None or p.skip_shift is not None:
+        raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
+    return v2v_conv3_wide(h, p.packed2, p.scale2, p.shift2, x)
+
+
+class Res3DBlockWideCL(nn.Module):
+    """Eval-mode replacement of a Res3DBlock(32 | 64, 64) on a channels-last bf16 volume:
+    ``Res3DBlockWideCL.from_reference(block)(x_cl)``."""
+
+    def __init__(self, params):
+        super().__init__()
+        for name, t in zip(Res3DParams._fields, Res3DParams(*params)):
+            self.register_buffer(name, t)
+
+    @classmethod
+    def from_reference(cls, block, device="cuda"):
+        return cls(fold_res3d_block_wide(block, device=device))
+
+    @property
+    def params(self):
+        return Res3DParams(*(getattr(self, name) for name in Res3DParams._fields))
+
+    def forward(self, x_cl):
+        return res3d_block_wide(x_cl, self.params)
+
+
+def upsample2_add(x_cl, params, skip=None):
+    """(B, V, V, V, 64) bf16 channels-last -> (B, 2V, 2V, 2V, 32) bf16: an eval-mode
+    Upsample3DBlock(64, 32) and the ``+ skip`` behind it in one launch (mvn_v2v_upsample2):
+    bf16(relu(bn(conv_transpose(x))) + skip), the ReLU before the add, one rounding.  ``params``
+    from ``fold_upsample_block``; ``skip`` (B, 2V, 2V, 2V, 32) bf16, or None for no add.  V is a
+    multiple of 16 in [16, 128].  Inference-only."""
+    from . import _ops
+    what = "upsample2_add"
+    p = UpsampleParams(*params)
+    _inference_only(what, x_cl, *p, skip, instead="the model's own Upsample3DBlock, which autograd records")
+    x = _wide_volume(what, x_cl, channels=(UP_CIN,))
+    packed, scale, shift = _wide_params(what, p.packed, p.scale, p.shift, (2, 16, 64, 8), UP_COUT)
+    if skip is not None:
+        skip = _wide_volume(what, skip, "skip", (UP_COUT,), vmax=256)
+        B, V = x.shape[0], x.shape[1]
+        if tuple(skip.shape[:4]) != (B, 2 * V, 2 * V, 2 * V):
+            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)} upsampled")
+    return _ops.call(_ops.v2v_upsample2, x, packed, scale, shift, skip)
+
+
+class Upsample3DBlockCL(nn.Module):
+    """Eval-mode replacement of Upsample3DBlock(64, 32) with the ``+ skip`` behind it."""
+
+    def __init__(self, params):
+        super().__init__()
+        for name, t in zip(UpsampleParams._fields, UpsampleParams(*params)):
+            self.register_buffer(name, t)
+
+    @classmethod
+    def from_reference(cls, block, device="cuda"):
+        return cls(fold_upsample_block(block, device=device))
+
+    @property
+    def params(self):
+        return UpsampleParams(self.packed, self.scale, self.shift)
+
+    def forward(self, x_cl, skip=None):
+        return upsample2_add(x_cl, self.params, skip)
+
+
+def v2v_interior_deep(encoder_decoder, x):
+    """EncoderDecorder.forward (v2v.py:108-132) from ``encoder_pool2`` through
+    ``decoder_upsample2``: the levels below the first pooled one (16^3 and below at V = 64, 128
+    channels), with the model's own modules.  x is ``encoder_res1``'s output (B, 64, V/2, V/2,
+    V/2); the result has its shape and still lacks ``+ skip_x2``."""
     ed = encoder_decoder
-    x = ed.encoder_res1(ed.encoder_pool1(x))
-    s2 = ed.skip_res2(x)
     x = ed.encoder_res2(ed.encoder_pool2(x))
     s3 = ed.skip_res3(x)
     x = ed.encoder_res3(ed.encoder_pool3(x))
@@ -582,7 +844,16 @@ def v2v_interior(encoder_decoder, x):
     x = ed.decoder_upsample5(ed.decoder_res5(x)) + s5
     x = ed.decoder_upsample4(ed.decoder_res4(x)) + s4
     x = ed.decoder_upsample3(ed.decoder_res3(x)) + s3
-    x = ed.decoder_upsample2(ed.decoder_res2(x)) + s2
+    return ed.decoder_upsample2(ed.decoder_res2(x))
+
+
+def v2v_interior(encoder_decoder, x):
+    """The pooled part of EncoderDecorder.forward (v2v.py:105-135): everything between skip_res1
+    and the last ``+ skip_x1``, 32^3 and below at V = 64, with the model's own modules."""
+    ed = encoder_decoder
+    x = ed.encoder_res1(ed.encoder_pool1(x))
+    s2 = ed.skip_res2(x)
+    x = v2v_interior_deep(ed, x) + s2
     return ed.decoder_upsample1(ed.decoder_res1(x))
 
 
@@ -606,28 +877,51 @@ class V2VEval(nn.Module):
     5. ``back_layers[0]``: ``res3d_block``;
     6. ``v2v_head_softargmax(channels_last=True)``.
 
+    With ``from_reference(..., half_res="kernels")`` steps 3 and 4 shrink to the levels below the
+    first pooled one: ``max_pool2_cl``, ``encoder_res1``, ``skip_res2`` and ``decoder_res1`` as
+    ``res3d_block_wide`` and ``decoder_upsample1`` with ``+ skip_x1`` as ``upsample2_add`` run on
+    kernels, and the torch glue (cast to NCDHW ``interior_dtype``, ``+ skip_x2``,
+    cast back) touches (B, V/2, V/2, V/2, 64) volumes only, an eighth of the traffic above.
+
     The interior modules are a copy of the model's (its parameters frozen), so later changes to
     the model do not reach this module.  Inference-only."""
 
-    def __init__(self, front, front_res, skip_res1, interior, back_res, head, interior_dtype=torch.float32):
+    def __init__(self, front, front_res, skip_res1, interior, back_res, head, interior_dtype=torch.float32,
+                 half_res=None):
         super().__init__()
         self.front, self.front_res, self.skip_res1 = front, nn.ModuleList(front_res), skip_res1
         self.interior, self.back_res, self.head = interior, back_res, head
         self.interior_dtype = interior_dtype
+        # half_res="kernels": (encoder_res1, skip_res2, decoder_res1, decoder_upsample1) on the
+        # kernels of the first pooled level; None: that level runs in ``interior`` (torch)
+        self.half_res = nn.ModuleList(half_res) if half_res is not None else None
 
     @classmethod
-    def from_reference(cls, v2v_model, interior_dtype=torch.float32, device="cuda"):
+    def from_reference(cls, v2v_model, interior_dtype=torch.float32, device="cuda", half_res="torch"):
+        """``half_res="torch"`` (the default) runs the whole pooled interior with the model's torch
+        modules; ``"kernels"`` runs its first level (V/2, 64 channels) and both of its boundaries on
+        this package's kernels and leaves the levels below to torch."""
         import copy
+        if half_res not in ("torch", "kernels"):
+            raise ValueError(f"half_res must be 'torch' or 'kernels', got {half_res!r}")
         fl, ed = v2v_model.front_layers, v2v_model.encoder_decoder
         if len(fl) != 4:
             raise RuntimeError(f"expected front_layers of 4 modules, got {len(fl)}")
         interior = copy.deepcopy(ed).eval().to(device=device, dtype=interior_dtype).requires_grad_(False)
         del interior.skip_res1                              # runs on the kernel
+        half = None
+        if half_res == "kernels":
+            half = [Res3DBlockWideCL.from_reference(ed.encoder_res1, device=device),
+                    Res3DBlockWideCL.from_reference(ed.skip_res2, device=device),
+                    Res3DBlockWideCL.from_reference(ed.decoder_res1, device=device),
+                    Upsample3DBlockCL.from_reference(ed.decoder_upsample1, device=device)]
+            for name in ("encoder_res1", "skip_res2", "decoder_res1", "decoder_upsample1"):
+                delattr(interior, name)                     # run on the kernels
         return cls(Basic3DBlockFront.from_reference(fl[0], device=device),
                    [Res3DBlockCL.from_reference(fl[i], device=device) for i in (1, 2, 3)],
                    Res3DBlockCL.from_reference(ed.skip_res1, device=device), interior,
                    Res3DBlockCL.from_reference(v2v_model.back_layers[0], device=device),
-                   V2VHead.from_reference(v2v_model, device=device), interior_dtype)
+                   V2VHead.from_reference(v2v_model, device=device), interior_dtype, half)
 
     def trunk(self, vol_cl):
         """(B, V, V, V, 32) bf16 unprojected volume -> the (B, V, V, V, 32) bf16 input of the head."""
@@ -636,6 +930,16 @@ class V2VEval(nn.Module):
         for blk in self.front_res:
             h = blk(h)
         skip_x1 = self.skip_res1(h)
+        if self.half_res is not None:
+            # no torch pass over a full-resolution volume: the glue below touches (B, V/2, V/2,
+            # V/2, 64) volumes only
+            encoder_res1, skip_res2, decoder_res1, upsample1 = self.half_res
+            e1 = encoder_res1(max_pool2_cl(h))
+            s2 = skip_res2(e1)
+            d = v2v_interior_deep(self.interior, e1.permute(0, 4, 1, 2, 3).to(self.interior_dtype))
+            d = d + s2.permute(0, 4, 1, 2, 3)
+            d1 = decoder_res1(d.permute(0, 2, 3, 4, 1).to(torch.bfloat16).contiguous())
+            return self.back_res(upsample1(d1, skip_x1))
         x = v2v_interior(self.interior, h.permute(0, 4, 1, 2, 3).to(self.interior_dtype))
         x = x + skip_x1.permute(0, 4, 1, 2, 3)
         return self.back_res(x.permute(0, 2, 3, 4, 1).to(torch.bfloat16).contiguous())
