@@ -32,6 +32,9 @@
  *                        <- mvn/models/v2v.py:45-65, 105-135 (the encoder-decoder's first pooled
  *                           level: encoder_pool1, encoder_res1, skip_res2, decoder_res1 and
  *                           decoder_upsample1 with the last `+ skip_x1`; eval mode)
+ *   mvn_v2v_conv3_deep, mvn_v2v_upsample2_deep
+ *                        <- mvn/models/v2v.py:20-42, 53-65, 108-132 (the 128-channel levels below:
+ *                           encoder_res2 ... decoder_upsample2 with their `+ skip`s; eval mode)
  *   mvn_triangulate_ransac <-mvn/models/triangulation.py:54-128 (the RANSAC baseline's host
  *                           loop: hypotheses, inlier DLT, Huber refinement)
  *   mvn_reprojection_error <- mvn/utils/multiview.py:177-184 calc_reprojection_error_matrix(...)
@@ -440,6 +443,68 @@ int mvn_v2v_conv3_wide(const void* x, int cin, const void* weight_packed, const 
 size_t mvn_v2v_upsample2_packed_weight_bytes(void);
 int mvn_v2v_upsample2(const void* x, const void* weight_packed, const float* scale, const float* shift,
                       const void* skip, void* out, int B, int V, void* stream);
+
+/*
+ * mvn_v2v_conv3 with 128 output channels, for the Res3DBlocks of the levels below the first pooled
+ * one (Res3DBlock(64, 128) and Res3DBlock(128, 128), v2v.py:20-42): Conv3d(cin -> 128, k = 3,
+ * stride 1, zero padding 1) + BatchNorm3d, an optional residual, ReLU.  The arithmetic per output
+ * voxel and channel is mvn_v2v_conv3's (acc, pre, r, y above; the pointwise skip's acc_s is two
+ * K = 32 MFMA passes over its 64 channels), with
+ *   x              (B, D, D, D, cin) bf16, cin 64 | 128;  D any integer in [1, 64]
+ *   weight_packed  mvn_v2v_conv3_deep_packed_weight_bytes(cin) = 27 * (cin / 32) * 8 * 64 * 8 * 2
+ *                  bytes (442,368 | 884,736): bf16 weights as
+ *                  [tap = (dx*3 + dy)*3 + dz][kp 0..cin/32-1][m 0..7][lane 0..63][j 0..7]
+ *                    = W[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]
+ *                  (W the Conv3d weight (128, cin, 3, 3, 3); tap (dx, dy, dz) multiplies input
+ *                  voxel (x + dx - 1, y + dy - 1, z + dz - 1); a tap outside the volume contributes
+ *                  zero and never reads the neighbouring frame)
+ *   scale, shift   (128) f32: BN and the conv bias folded
+ *   skip           NONE: NULL.  IDENTITY: (B, D, D, D, 128) bf16, skip_cin 128.  POINTWISE:
+ *                  (B, D, D, D, 64) bf16, skip_cin 64.  Must not overlap out.
+ *   skip_weight_packed  POINTWISE only (NULL otherwise),
+ *                  mvn_v2v_conv3_deep_skip_packed_weight_bytes(64) = 2 * 8 * 64 * 8 * 2 bytes:
+ *                  [kp 0..1][m 0..7][lane 0..63][j 0..7] = Ws[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j]
+ *                  (Ws the 1x1x1 Conv3d weight (128, 64))
+ *   skip_scale, skip_shift  POINTWISE only (NULL otherwise): (128) f32
+ *   out            (B, D, D, D, 128) bf16
+ * Volumes and packed weights are 16-byte aligned.  Deterministic: every output is one wave's sum
+ * in a fixed order (no atomics), so two calls on the same data return the same bits.  A NaN or
+ * infinite input voxel reaches exactly its 3^3 neighbourhood clipped to its own frame, in all 128
+ * channels; a non-finite skip voxel exactly its own voxel.  Checked before any HIP call, argument
+ * errors first: MVN_ERR_ARG for a null required pointer, an unknown skip_mode or skip pointers that
+ * contradict the mode; MVN_ERR_SHAPE for B < 1, D outside [1, 64], a cin other than 64 / 128, a
+ * skip_cin other than 128 with IDENTITY or other than 64 with POINTWISE, or B * D^3 above
+ * INT_MAX / 8.  The size functions return 0 for a cin they do not take.  Stream-ordered, allocates
+ * nothing, reentrant.
+ */
+size_t mvn_v2v_conv3_deep_packed_weight_bytes(int cin);
+size_t mvn_v2v_conv3_deep_skip_packed_weight_bytes(int cin);
+int mvn_v2v_conv3_deep(const void* x, int cin, const void* weight_packed, const float* scale, const float* shift,
+                       int skip_mode, const void* skip, int skip_cin, const void* skip_weight_packed,
+                       const float* skip_scale, const float* skip_shift, void* out, int B, int D, void* stream);
+
+/*
+ * Upsample3DBlock(128, cout, 2, 2), eval mode (v2v.py:53-65), fused with the `+ skip` behind it
+ * (v2v.py:126-132): mvn_v2v_upsample2's arithmetic (acc over the 128 input channels in four K = 32
+ * MFMA passes, pre, u, one rounding after the add) with
+ *   x              (B, D, D, D, 128) bf16;  D any integer in [1, 64]
+ *   cout           64 | 128
+ *   weight_packed  mvn_v2v_upsample2_deep_packed_weight_bytes(cout) = 4 * 8 * (cout / 16) * 64 * 8 * 2
+ *                  bytes: bf16 as [kp 0..3][m 0..8 cout/16 - 1][lane 0..63][j 0..7]
+ *                    = W[32 kp + 8 (lane >> 4) + j][16 (m % (cout / 16)) + (lane & 15)][dx][dy][dz],
+ *                  (dx*2 + dy)*2 + dz = m / (cout / 16)  (W the ConvTranspose3d weight
+ *                  (128, cout, 2, 2, 2))
+ *   scale, shift   (cout) f32: BN and the ConvTranspose bias folded
+ *   skip           (B, 2D, 2D, 2D, cout) bf16, or NULL for no add; must not overlap out
+ *   out            (B, 2D, 2D, 2D, cout) bf16
+ * A non-finite input voxel reaches exactly its own 2x2x2 outputs (all channels), a non-finite skip
+ * voxel exactly itself.  Deterministic.  MVN_ERR_ARG for a null required pointer; MVN_ERR_SHAPE
+ * for B < 1, D outside [1, 64], another cout, or B * D^3 above INT_MAX / 8.  The size function
+ * returns 0 for another cout.  Stream-ordered, allocates nothing, reentrant.
+ */
+size_t mvn_v2v_upsample2_deep_packed_weight_bytes(int cout);
+int mvn_v2v_upsample2_deep(const void* x, int cout, const void* weight_packed, const float* scale,
+                           const float* shift, const void* skip, void* out, int B, int D, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

@@ -391,6 +391,53 @@ def _(x, packed, scale, shift, skip):
     return x.new_empty((B, 2 * V, 2 * V, 2 * V, 32), dtype=torch.bfloat16)
 
 
+# --------------------------------------------------------------------------- V2V 128-channel levels
+@_op("v2v_conv3_deep")
+def v2v_conv3_deep(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip_mode: int, skip: Optional[Tensor],
+                   skip_packed: Optional[Tensor], skip_scale: Optional[Tensor],
+                   skip_shift: Optional[Tensor]) -> Tensor:
+    """x (B,D,D,D,cin) bf16, cin 64 | 128, any D in [1, 64] -> (B,D,D,D,128) bf16:
+    relu(bn(conv3d_3(x)) + skip term) (csrc/v2v_deep.hip); skip (B,D,D,D,128) with MVN_SKIP_IDENTITY,
+    (B,D,D,D,64) and its packed 1x1x1 weights, scale and shift with MVN_SKIP_POINTWISE."""
+    _require_gpu(x, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
+    B, D, cin = x.shape[0], x.shape[1], x.shape[4]
+    out = torch.empty((B, D, D, D, 128), dtype=torch.bfloat16, device=x.device)
+    if out.numel() == 0:                  # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_v2v_conv3_deep(
+        x.data_ptr(), cin, packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(skip_mode), _ptr(skip),
+        skip.shape[4] if skip is not None else 0, _ptr(skip_packed), _ptr(skip_scale), _ptr(skip_shift),
+        out.data_ptr(), B, D, _stream(x))
+    _lib.check(code, "mvn_v2v_conv3_deep")
+    return out
+
+
+@v2v_conv3_deep.register_fake
+def _(x, packed, scale, shift, skip_mode, skip, skip_packed, skip_scale, skip_shift):
+    return x.new_empty((*x.shape[:4], 128), dtype=torch.bfloat16)
+
+
+@_op("v2v_upsample2_deep")
+def v2v_upsample2_deep(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip: Optional[Tensor]) -> Tensor:
+    """x (B,D,D,D,128) bf16 -> (B,2D,2D,2D,cout) bf16, cout = scale.numel() (64 | 128):
+    relu(bn(conv_transpose3d_2(x))) + skip (csrc/v2v_deep.hip); skip (B,2D,2D,2D,cout) bf16 or None."""
+    _require_gpu(x, packed, scale, shift, skip)
+    B, D, cout = x.shape[0], x.shape[1], scale.shape[0]
+    out = torch.empty((B, 2 * D, 2 * D, 2 * D, cout), dtype=torch.bfloat16, device=x.device)
+    if out.numel() == 0:                  # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_v2v_upsample2_deep(x.data_ptr(), cout, packed.data_ptr(), scale.data_ptr(),
+                                              shift.data_ptr(), _ptr(skip), out.data_ptr(), B, D, _stream(x))
+    _lib.check(code, "mvn_v2v_upsample2_deep")
+    return out
+
+
+@v2v_upsample2_deep.register_fake
+def _(x, packed, scale, shift, skip):
+    B, D = x.shape[0], x.shape[1]
+    return x.new_empty((B, 2 * D, 2 * D, 2 * D, scale.shape[0]), dtype=torch.bfloat16)
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,

@@ -18,7 +18,10 @@ Between them, the five ``Res3DBlock``s that run at the full resolution (``front_
 whole eval-mode V2V with the soft-argmax, the pooled interior alone left to torch.  With
 ``half_res="kernels"`` the interior's first level and its boundaries run on kernels too:
 ``max_pool2_cl``, ``v2v_conv3_wide`` / ``res3d_block_wide`` / ``Res3DBlockWideCL`` and
-``upsample2_add`` (csrc/v2v_interior.hip).
+``upsample2_add`` (csrc/v2v_interior.hip).  With ``deep="kernels"`` on top of it
+the 128-channel levels below run on kernels as well, at any extent from 64 down to 1:
+``v2v_conv3_deep`` / ``res3d_block_deep`` / ``Res3DBlockDeepCL``, ``upsample2_add_deep`` and
+``v2v_interior_deep_cl`` (csrc/v2v_deep.hip), and ``V2VEval`` runs no torch module.
 """
 from __future__ import annotations
 
@@ -827,6 +830,283 @@ class Upsample3DBlockCL(nn.Module):
         return upsample2_add(x_cl, self.params, skip)
 
 
+# --------------------------------------------------------------------------- 128-channel levels
+# encoder_pool2 ... decoder_upsample2 (mvn/models/v2v.py:108-132): the Res3DBlocks with 128 output
+# channels and the upsamples that take 128 channels, at any extent D in [1, 64], on channels-last
+# bf16 volumes (csrc/v2v_deep.hip).
+DEEP_C = 128
+DEEP_MAX_D = 64
+
+
+def pack_conv3_deep_weight(w):
+    """(128, cin, 3, 3, 3) float64, cin 64 | 128 -> (27, cin / 32, 8, 64, 8) bf16 as mvn_v2v_conv3_deep
+    reads it: [tap = (dx*3 + dy)*3 + dz][kp][m][lane][j]
+    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]."""
+    cin = w.shape[1]
+    wt = w.reshape(DEEP_C, cin, 27).permute(2, 0, 1)                                # [tap][cout][cin]
+    row, k = _mfma_a_rows()
+    packed = torch.stack([torch.stack([wt[:, (16 * m + row).view(64, 1).expand(64, 8), 32 * kp + k]
+                                       for m in range(8)], dim=1) for kp in range(cin // 32)], dim=1)
+    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+
+
+def pack_pointwise_skip_deep_weight(w):
+    """(128, 64) float64 -> (2, 8, 64, 8) bf16: [kp][m][lane][j]
+    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j]."""
+    row, k = _mfma_a_rows()
+    packed = torch.stack([torch.stack([w[(16 * m + row).view(64, 1).expand(64, 8), 32 * kp + k] for m in range(8)])
+                          for kp in range(2)])
+    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+
+
+def pack_upsample_deep_weight(w):
+    """(128, cout, 2, 2, 2) float64 ConvTranspose3d weight, cout 64 | 128 -> (4, 8 cout / 16, 64, 8)
+    bf16 as mvn_v2v_upsample2_deep reads it, with H = cout / 16 channel tiles per offset:
+    [kp][m][lane][j] = w[32 kp + 8 (lane >> 4) + j][16 (m % H) + (lane & 15)][dx][dy][dz]
+    with (dx*2 + dy)*2 + dz = m // H."""
+    cout = w.shape[1]
+    H = cout // 16
+    wt = w.reshape(DEEP_C, cout, 8).permute(2, 1, 0)                                # [pos][cout][cin]
+    row, k = _mfma_a_rows()
+    packed = torch.stack([torch.stack([wt[m // H][(16 * (m % H) + row).view(64, 1).expand(64, 8), 32 * kp + k]
+                                       for m in range(8 * H)]) for kp in range(4)])
+    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+
+
+def _fold_conv_bn_deep(conv, bn, what, ks, cins):
+    """(f64 weight, f64 scale, f64 shift) of an eval-mode Conv3d(cins -> 128, ks) + BatchNorm3d(128)."""
+    w = getattr(conv, "weight", None)
+    want = " | ".join(map(str, cins))
+    if not isinstance(conv, nn.Conv3d) or w.shape[0] != DEEP_C or w.shape[1] not in cins or tuple(w.shape[2:]) != (ks,) * 3:
+        got = tuple(w.shape) if w is not None else type(conv).__name__
+        raise RuntimeError(f"{what}: expected a ({DEEP_C}, {want}, {ks}, {ks}, {ks}) Conv3d weight, got {got}")
+    w = w.detach().to(torch.float64).cpu()
+    pad = (ks - 1) // 2
+    if tuple(conv.stride) != (1, 1, 1) or tuple(conv.padding) != (pad,) * 3 or tuple(conv.dilation) != (1, 1, 1):
+        raise RuntimeError(f"{what}: expected stride 1, padding {pad} and no dilation")
+    if bn.running_mean is None or tuple(bn.running_mean.shape) != (DEEP_C,):
+        raise RuntimeError(f"{what}: expected a BatchNorm3d({DEEP_C}) with running statistics")
+    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(DEEP_C, dtype=torch.float64)
+    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
+    return w, s, shift
+
+
+def fold_res3d_block_deep(block, device="cuda"):
+    """An eval-mode module with Res3DBlock's attributes and 64 | 128 -> 128 channels (``skip_con``
+    [conv 1x1x1, BN] for 64, empty for 128) -> ``Res3DParams`` on ``device``: folded in float64
+    exactly as ``fold_res3d_block_wide``, packed as mvn_v2v_conv3_deep expects
+    (``pack_conv3_deep_weight``, ``pack_pointwise_skip_deep_weight``)."""
+    rb, sk = getattr(block, "res_branch", None), getattr(block, "skip_con", None)
+    if rb is None or sk is None or len(rb) != 5 or len(sk) not in (0, 2):
+        raise RuntimeError("expected a module with Res3DBlock's res_branch of 5 modules and skip_con of 0 or 2, got "
+                           + type(block).__name__)
+    w1, s1, t1 = _fold_conv_bn_deep(rb[0], rb[1], "res_branch[0]", 3, (64, 128))
+    w2, s2, t2 = _fold_conv_bn_deep(rb[3], rb[4], "res_branch[3]", 3, (128,))
+    cin = w1.shape[1]
+    dev = torch.device(device)
+    skip = (None, None, None)
+    if len(sk) == 2:
+        ws, ss, ts = _fold_conv_bn_deep(sk[0], sk[1], "skip_con[0]", 1, (64,))
+        if cin != 64:
+            raise RuntimeError(f"a block with a 1x1x1 skip_con must take 64 channels, got {cin}")
+        skip = (pack_pointwise_skip_deep_weight(ws.reshape(DEEP_C, 64)).to(dev), ss.float().to(dev), ts.float().to(dev))
+    elif cin != DEEP_C:
+        raise RuntimeError(f"a block with an empty skip_con must take {DEEP_C} channels, got {cin}")
+    return Res3DParams(pack_conv3_deep_weight(w1).to(dev), s1.float().to(dev), t1.float().to(dev),
+                       pack_conv3_deep_weight(w2).to(dev), s2.float().to(dev), t2.float().to(dev), *skip)
+
+
+def fold_upsample_block_deep(block, device="cuda"):
+    """An eval-mode module with Upsample3DBlock's attributes (``block[0..2]`` = ConvTranspose3d(128,
+    64 | 128, 2, stride 2), BatchNorm3d, ReLU) -> ``UpsampleParams`` on ``device``: the ConvTranspose
+    bias and the BN folded in float64, the weights rounded to bf16 and packed as
+    mvn_v2v_upsample2_deep expects (``pack_upsample_deep_weight``)."""
+    seq = getattr(block, "block", None)
+    if seq is None or len(seq) != 3 or not isinstance(seq[0], nn.ConvTranspose3d):
+        raise RuntimeError("expected block = [ConvTranspose3d, BatchNorm3d, ReLU]")
+    conv, bn = seq[0], seq[1]
+    w = conv.weight.detach().to(torch.float64).cpu()
+    if w.dim() != 5 or w.shape[0] != DEEP_C or w.shape[1] not in (64, 128) or tuple(w.shape[2:]) != (2, 2, 2):
+        raise RuntimeError(f"block[0]: expected a ({DEEP_C}, 64 | 128, 2, 2, 2) ConvTranspose3d weight, got {tuple(w.shape)}")
+    cout = w.shape[1]
+    if (tuple(conv.stride) != (2, 2, 2) or tuple(conv.padding) != (0, 0, 0) or tuple(conv.output_padding) != (0, 0, 0)
+            or tuple(conv.dilation) != (1, 1, 1) or conv.groups != 1):
+        raise RuntimeError("block[0]: expected stride 2, no padding, no output padding, no dilation, one group")
+    if bn.running_mean is None or tuple(bn.running_mean.shape) != (cout,):
+        raise RuntimeError(f"block[1]: expected a BatchNorm3d({cout}) with running statistics")
+    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(cout, dtype=torch.float64)
+    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
+    dev = torch.device(device)
+    return UpsampleParams(pack_upsample_deep_weight(w).to(dev), s.float().to(dev), shift.float().to(dev))
+
+
+def _deep_volume(what, x, name="x_cl", channels=(64, 128), dmax=DEEP_MAX_D):
+    """Checked contiguous (B, D, D, D, C) bf16 volume of the 128-channel levels' kernels."""
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"{what}: {name} must be bfloat16, got {x.dtype}")
+    if x.dim() != 5 or x.shape[4] not in channels or len(set(x.shape[1:4])) != 1:
+        raise RuntimeError(f"{what}: {name} must be (B, D, D, D, {' | '.join(map(str, channels))}), got {tuple(x.shape)}")
+    if not 1 <= x.shape[1] <= dmax:
+        raise RuntimeError(f"{what}: {name}: D must be in [1, {dmax}], got {x.shape[1]}")
+    return x.contiguous()
+
+
+def v2v_conv3_deep(x_cl, packed, scale, shift, skip=None, skip_packed=None, skip_scale=None, skip_shift=None):
+    """(B, D, D, D, 64 | 128) bf16 channels-last -> (B, D, D, D, 128) bf16: one launch of
+    relu(bn(conv3d_3(x)) + skip term) (mvn_v2v_conv3_deep, eval mode).  Without ``skip`` there is
+    no residual; ``skip`` (B, D, D, D, 128) alone is added as it is (identity); ``skip``
+    (B, D, D, D, 64) with ``skip_packed``, ``skip_scale``, ``skip_shift`` goes through its folded
+    1x1x1 conv + BN.  D is any integer in [1, 64].  Non-finite voxels follow torch (mvn_hip.h);
+    two calls on the same data return the same bits.  Inference-only."""
+    from . import _ops
+    what = "v2v_conv3_deep"
+    _inference_only(what, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift,
+                    instead="the model's own Res3DBlock, which autograd records")
+    x = _deep_volume(what, x_cl)
+    packed, scale, shift = _wide_params(what, packed, scale, shift, (27, x.shape[4] // 32, 8, 64, 8), DEEP_C)
+    pw = (skip_packed, skip_scale, skip_shift)
+    if skip is None:
+        if any(t is not None for t in pw):
+            raise RuntimeError(f"{what}: skip weights without a skip volume")
+        mode = SKIP_NONE
+    else:
+        mode = SKIP_POINTWISE if skip_packed is not None else SKIP_IDENTITY
+        skip = _deep_volume(what, skip, "skip", (64,) if mode == SKIP_POINTWISE else (128,))
+        if tuple(skip.shape[:4]) != tuple(x.shape[:4]):
+            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)}")
+        if mode == SKIP_POINTWISE:
+            if skip_scale is None or skip_shift is None:
+                raise RuntimeError(f"{what}: a pointwise skip needs skip_packed, skip_scale and skip_shift")
+            pw = _wide_params(what, skip_packed, skip_scale, skip_shift, (2, 8, 64, 8), DEEP_C)
+        elif any(t is not None for t in pw):
+            raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
+    return _ops.call(_ops.v2v_conv3_deep, x, packed, scale, shift, mode, skip, *pw)
+
+
+def res3d_block_deep(x_cl, params):
+    """A whole eval-mode Res3DBlock(64 | 128, 128) as two ``v2v_conv3_deep`` launches: x_cl
+    (B, D, D, D, 64 | 128) bf16 channels-last -> (B, D, D, D, 128) bf16, ``params`` from
+    ``fold_res3d_block_deep``.  The hidden volume is a torch allocation (1 MB per frame at 16^3).
+    Inference-only."""
+    what = "res3d_block_deep"
+    p = Res3DParams(*params)
+    _inference_only(what, x_cl, *p, instead="the model's own Res3DBlock, which autograd records")
+    pointwise = p.skip_packed is not None
+    x = _deep_volume(what, x_cl, channels=(64,) if pointwise else (128,))
+    h = v2v_conv3_deep(x, p.packed1, p.scale1, p.shift1)
+    if pointwise:
+        return v2v_conv3_deep(h, p.packed2, p.scale2, p.shift2, x, p.skip_packed, p.skip_scale, p.skip_shift)
+    if p.skip_scale is not None or p.skip_shift is not None:
+        raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
+    return v2v_conv3_deep(h, p.packed2, p.scale2, p.shift2, x)
+
+
+class Res3DBlockDeepCL(nn.Module):
+    """Eval-mode replacement of a Res3DBlock(64 | 128, 128) on a channels-last bf16 volume:
+    ``Res3DBlockDeepCL.from_reference(block)(x_cl)``."""
+
+    def __init__(self, params):
+        super().__init__()
+        for name, t in zip(Res3DParams._fields, Res3DParams(*params)):
+            self.register_buffer(name, t)
+
+    @classmethod
+    def from_reference(cls, block, device="cuda"):
+        return cls(fold_res3d_block_deep(block, device=device))
+
+    @property
+    def params(self):
+        return Res3DParams(*(getattr(self, name) for name in Res3DParams._fields))
+
+    def forward(self, x_cl):
+        return res3d_block_deep(x_cl, self.params)
+
+
+def upsample2_add_deep(x_cl, params, skip=None):
+    """(B, D, D, D, 128) bf16 channels-last -> (B, 2D, 2D, 2D, cout) bf16, cout 64 | 128: an
+    eval-mode Upsample3DBlock(128, cout) and the ``+ skip`` behind it in one launch
+    (mvn_v2v_upsample2_deep): bf16(relu(bn(conv_transpose(x))) + skip), the ReLU before the add, one
+    rounding.  ``params`` from ``fold_upsample_block_deep``; ``skip`` (B, 2D, 2D, 2D, cout) bf16, or
+    None for no add.  D is any integer in [1, 64].  Inference-only."""
+    from . import _ops
+    what = "upsample2_add_deep"
+    p = UpsampleParams(*params)
+    _inference_only(what, x_cl, *p, skip, instead="the model's own Upsample3DBlock, which autograd records")
+    x = _deep_volume(what, x_cl, channels=(DEEP_C,))
+    cout = p.scale.shape[0] if p.scale.dim() == 1 else -1
+    if cout not in (64, 128):
+        raise RuntimeError(f"{what}: scale and shift must be (64 | 128,), got {tuple(p.scale.shape)}")
+    packed, scale, shift = _wide_params(what, p.packed, p.scale, p.shift, (4, 8 * cout // 16, 64, 8), cout)
+    if skip is not None:
+        skip = _deep_volume(what, skip, "skip", (cout,), dmax=2 * DEEP_MAX_D)
+        B, D = x.shape[0], x.shape[1]
+        if tuple(skip.shape[:4]) != (B, 2 * D, 2 * D, 2 * D):
+            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)} upsampled")
+    return _ops.call(_ops.v2v_upsample2_deep, x, packed, scale, shift, skip)
+
+
+class Upsample3DBlockDeepCL(nn.Module):
+    """Eval-mode replacement of Upsample3DBlock(128, 64 | 128) with the ``+ skip`` behind it."""
+
+    def __init__(self, params):
+        super().__init__()
+        for name, t in zip(UpsampleParams._fields, UpsampleParams(*params)):
+            self.register_buffer(name, t)
+
+    @classmethod
+    def from_reference(cls, block, device="cuda"):
+        return cls(fold_upsample_block_deep(block, device=device))
+
+    @property
+    def params(self):
+        return UpsampleParams(self.packed, self.scale, self.shift)
+
+    def forward(self, x_cl, skip=None):
+        return upsample2_add_deep(x_cl, self.params, skip)
+
+
+# the folded modules of ``V2VEval.deep`` in the order ``v2v_interior_deep_cl`` takes them
+DEEP_RES = ("encoder_res2", "skip_res3", "encoder_res3", "skip_res4", "encoder_res4", "skip_res5", "encoder_res5",
+            "mid_res", "decoder_res5", "decoder_res4", "decoder_res3", "decoder_res2")
+DEEP_UP = ("decoder_upsample5", "decoder_upsample4", "decoder_upsample3", "decoder_upsample2")
+
+
+def fold_deep_levels(encoder_decoder, device="cuda"):
+    """The Res3DBlocks ``DEEP_RES`` and the upsamples ``DEEP_UP`` of an EncoderDecorder as
+    ``Res3DBlockDeepCL`` and ``Upsample3DBlockDeepCL``, in that order: what ``v2v_interior_deep_cl``
+    takes."""
+    ed = encoder_decoder
+    return ([Res3DBlockDeepCL.from_reference(getattr(ed, name), device=device) for name in DEEP_RES]
+            + [Upsample3DBlockDeepCL.from_reference(getattr(ed, name), device=device) for name in DEEP_UP])
+
+
+def v2v_interior_deep_cl(deep, e1_cl, s2_cl):
+    """The data flow of ``v2v_interior_deep`` on channels-last bf16 volumes with the folded modules
+    ``deep`` (``fold_deep_levels``): e1_cl (B, D, D, D, 64), ``encoder_res1``'s output, and s2_cl,
+    ``skip_res2``'s output of the same shape -> (B, D, D, D, 64) with ``+ skip_x2`` already added:
+    every ``+ skip`` is fused into the upsample before it.  D is a multiple of 16 up to 128 (four
+    pools; the deepest level is D / 16).  No torch arithmetic: pools, ``res3d_block_deep`` and
+    ``upsample2_add_deep`` only."""
+    if len(deep) != len(DEEP_RES) + len(DEEP_UP):
+        raise RuntimeError(f"expected the {len(DEEP_RES) + len(DEEP_UP)} modules of fold_deep_levels, got {len(deep)}")
+    (encoder_res2, skip_res3, encoder_res3, skip_res4, encoder_res4, skip_res5, encoder_res5, mid_res,
+     decoder_res5, decoder_res4, decoder_res3, decoder_res2, up5, up4, up3, up2) = deep
+    x = encoder_res2(max_pool2_cl(e1_cl))
+    s3 = skip_res3(x)
+    x = encoder_res3(max_pool2_cl(x))
+    s4 = skip_res4(x)
+    x = encoder_res4(max_pool2_cl(x))
+    s5 = skip_res5(x)
+    x = encoder_res5(max_pool2_cl(x))
+    x = mid_res(x)
+    x = up5(decoder_res5(x), s5)
+    x = up4(decoder_res4(x), s4)
+    x = up3(decoder_res3(x), s3)
+    return up2(decoder_res2(x), s2_cl)
+
+
 def v2v_interior_deep(encoder_decoder, x):
     """EncoderDecorder.forward (v2v.py:108-132) from ``encoder_pool2`` through
     ``decoder_upsample2``: the levels below the first pooled one (16^3 and below at V = 64, 128
@@ -883,11 +1163,16 @@ class V2VEval(nn.Module):
     kernels, and the torch glue (cast to NCDHW ``interior_dtype``, ``+ skip_x2``,
     cast back) touches (B, V/2, V/2, V/2, 64) volumes only, an eighth of the traffic above.
 
+    With ``deep="kernels"`` on top of that the levels below run on kernels too
+    (``v2v_interior_deep_cl``: ``max_pool2_cl``, ``res3d_block_deep`` and ``upsample2_add_deep`` with
+    every ``+ skip`` fused): steps 3 and 4 are gone, ``interior`` is None and no
+    ``torch.nn`` module runs.  V is then a multiple of 32.
+
     The interior modules are a copy of the model's (its parameters frozen), so later changes to
     the model do not reach this module.  Inference-only."""
 
     def __init__(self, front, front_res, skip_res1, interior, back_res, head, interior_dtype=torch.float32,
-                 half_res=None):
+                 half_res=None, deep=None):
         super().__init__()
         self.front, self.front_res, self.skip_res1 = front, nn.ModuleList(front_res), skip_res1
         self.interior, self.back_res, self.head = interior, back_res, head
@@ -895,15 +1180,25 @@ class V2VEval(nn.Module):
         # half_res="kernels": (encoder_res1, skip_res2, decoder_res1, decoder_upsample1) on the
         # kernels of the first pooled level; None: that level runs in ``interior`` (torch)
         self.half_res = nn.ModuleList(half_res) if half_res is not None else None
+        # deep="kernels": the folded modules of ``fold_deep_levels`` (the 128-channel levels on
+        # kernels, ``interior`` is None then); None: those levels run in ``interior`` (torch)
+        self.deep = nn.ModuleList(deep) if deep is not None else None
 
     @classmethod
-    def from_reference(cls, v2v_model, interior_dtype=torch.float32, device="cuda", half_res="torch"):
+    def from_reference(cls, v2v_model, interior_dtype=torch.float32, device="cuda", half_res="torch", deep="torch"):
         """``half_res="torch"`` (the default) runs the whole pooled interior with the model's torch
         modules; ``"kernels"`` runs its first level (V/2, 64 channels) and both of its boundaries on
-        this package's kernels and leaves the levels below to torch."""
+        this package's kernels and leaves the levels below to torch.
+        ``deep="kernels"`` (with ``half_res="kernels"`` only) runs those levels on kernels as well
+        (DESIGN.md §4.14): ``self.deep`` holds their folded modules, ``self.interior`` is None and no
+        torch module is left."""
         import copy
         if half_res not in ("torch", "kernels"):
             raise ValueError(f"half_res must be 'torch' or 'kernels', got {half_res!r}")
+        if deep not in ("torch", "kernels"):
+            raise ValueError(f"deep must be 'torch' or 'kernels', got {deep!r}")
+        if deep == "kernels" and half_res != "kernels":
+            raise ValueError(f"deep='kernels' requires half_res='kernels', got half_res={half_res!r}")
         fl, ed = v2v_model.front_layers, v2v_model.encoder_decoder
         if len(fl) != 4:
             raise RuntimeError(f"expected front_layers of 4 modules, got {len(fl)}")
@@ -917,11 +1212,14 @@ class V2VEval(nn.Module):
                     Upsample3DBlockCL.from_reference(ed.decoder_upsample1, device=device)]
             for name in ("encoder_res1", "skip_res2", "decoder_res1", "decoder_upsample1"):
                 delattr(interior, name)                     # run on the kernels
+        deep_modules = None
+        if deep == "kernels":
+            deep_modules, interior = fold_deep_levels(ed, device=device), None
         return cls(Basic3DBlockFront.from_reference(fl[0], device=device),
                    [Res3DBlockCL.from_reference(fl[i], device=device) for i in (1, 2, 3)],
                    Res3DBlockCL.from_reference(ed.skip_res1, device=device), interior,
                    Res3DBlockCL.from_reference(v2v_model.back_layers[0], device=device),
-                   V2VHead.from_reference(v2v_model, device=device), interior_dtype, half)
+                   V2VHead.from_reference(v2v_model, device=device), interior_dtype, half, deep_modules)
 
     def trunk(self, vol_cl):
         """(B, V, V, V, 32) bf16 unprojected volume -> the (B, V, V, V, 32) bf16 input of the head."""
@@ -936,6 +1234,9 @@ class V2VEval(nn.Module):
             encoder_res1, skip_res2, decoder_res1, upsample1 = self.half_res
             e1 = encoder_res1(max_pool2_cl(h))
             s2 = skip_res2(e1)
+            if self.deep is not None:
+                # no torch arithmetic at all between the pool and back_layers[0]
+                return self.back_res(upsample1(decoder_res1(v2v_interior_deep_cl(self.deep, e1, s2)), skip_x1))
             d = v2v_interior_deep(self.interior, e1.permute(0, 4, 1, 2, 3).to(self.interior_dtype))
             d = d + s2.permute(0, 4, 1, 2, 3)
             d1 = decoder_res1(d.permute(0, 2, 3, 4, 1).to(torch.bfloat16).contiguous())
