@@ -5,7 +5,7 @@
 #include <climits>
 #include <type_traits>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace mvn {
 namespace unproj {
@@ -203,8 +203,6 @@ __device__ __forceinline__ float aggregate(const float (&s)[NV], int N, const fl
   return r;
 }
 
-constexpr uint32_t kOob = 0x80000000u;            // buffer byte offset past any frame
-
 // 16-byte buffer store followed by two wait states.  A VMEM store of more than 8 bytes reads
 // its data VGPRs after issue; a VALU write to them in the next cycles (cdna_asm_programming.md
 // §4.1 rows 8/9) makes the store write the NEW value.  hipcc left that pair unpadded in the
@@ -237,15 +235,6 @@ __device__ __forceinline__ int wave_max_u(int v) {
   v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x118, 0xf, 0xf, false));
   return max(max(__builtin_amdgcn_readlane(v, 15), __builtin_amdgcn_readlane(v, 31)),
              max(__builtin_amdgcn_readlane(v, 47), __builtin_amdgcn_readlane(v, 63)));
-}
-
-// Buffer descriptor from block-uniform inputs, provably in SGPRs (cdna_hip_programming.md T20).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(a));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(a >> 32));
-  void* p = reinterpret_cast<void*>((uint64_t(hi) << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(p, 0, int(__builtin_amdgcn_readfirstlane(bytes)), 0x00020000);
 }
 
 // One voxel, all channels, taps gathered from global memory (oversize-footprint fallback).

@@ -32,26 +32,13 @@
 // load and one 8-byte store per channel tile.
 #include <climits>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace mvn {
 namespace {
 
 constexpr int CO = 128, NTAP = 27, MT = CO / 16;
 constexpr int kWaves = 4, kThreads = kWaves * kWave;
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4_t mfma(const uint4& a, const uint4& b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c,
-                                                 0, 0, 0);
-}
-
-__device__ __forceinline__ float bf16_of_pair(const uint2& q, int i) {
-  const uint32_t pair = i < 2 ? q.x : q.y;
-  return __uint_as_float((i & 1) ? (pair & 0xffff0000u) : (pair << 16));
-}
 
 template <int CIN, int MODE, int NG, int MTB>
 __global__ __launch_bounds__(kThreads) void v2v_conv3_deep(
@@ -164,6 +151,8 @@ __global__ __launch_bounds__(kThreads) void v2v_conv3_deep(
       if (!ok) continue;
       uint2 sk = make_uint2(0u, 0u);
       if constexpr (MODE == MVN_SKIP_IDENTITY) sk = *reinterpret_cast<const uint2*>(skip + vo * CO + ch);
+      // bn_skip_relu (mfma.hpp) written out: through the helper, four of this kernel's instantiations
+      // come out with two register quadruples exchanged
       float y[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -172,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void v2v_conv3_deep(
         if constexpr (MODE == MVN_SKIP_POINTWISE) r = r + __builtin_fmaf(accs[i], scale_s[ch + i], shift_s[ch + i]);
         y[i] = relu_keep_nan(r);
       }
-      *reinterpret_cast<uint2*>(out + vo * CO + ch) = make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+      *reinterpret_cast<uint2*>(out + vo * CO + ch) = pack_bf16x4(y);
     }
   }
 }
@@ -233,14 +222,10 @@ __global__ __launch_bounds__(kThreads) void v2v_upsample2_deep(const uint16_t* _
       MVN_DASSERT(ch + 4 <= COUT && o + 4 <= size_t(N) * 8 * COUT);
       uint2 sk = make_uint2(0u, 0u);
       if constexpr (SKIP) sk = *reinterpret_cast<const uint2*>(skip + o);
-      float yv[4];
+      float y[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float t = relu_keep_nan(__builtin_fmaf(acc[i], scale[ch + i], shift[ch + i]));
-        if constexpr (SKIP) t = t + bf16_of_pair(sk, i);
-        yv[i] = t;
-      }
-      *reinterpret_cast<uint2*>(out + o) = make_uint2(pack_bf16x2(yv[0], yv[1]), pack_bf16x2(yv[2], yv[3]));
+      for (int i = 0; i < 4; ++i) y[i] = bn_relu_add<SKIP>(acc, scale, shift, sk, i, ch);
+      *reinterpret_cast<uint2*>(out + o) = pack_bf16x4(y);
     }
   }
 }
@@ -291,11 +276,9 @@ template <int CIN>
 int launch_deep_mode(int skip_mode, const void* x, const void* wpk, const float* scale, const float* shift,
                      const void* skip, const void* wskip, const float* scale_s, const float* shift_s, void* out,
                      int D, int N, hipStream_t st) {
-  if (skip_mode == MVN_SKIP_NONE)
-    return launch_deep<CIN, MVN_SKIP_NONE>(x, wpk, scale, shift, skip, wskip, scale_s, shift_s, out, D, N, st);
-  if (skip_mode == MVN_SKIP_IDENTITY)
-    return launch_deep<CIN, MVN_SKIP_IDENTITY>(x, wpk, scale, shift, skip, wskip, scale_s, shift_s, out, D, N, st);
-  return launch_deep<CIN, MVN_SKIP_POINTWISE>(x, wpk, scale, shift, skip, wskip, scale_s, shift_s, out, D, N, st);
+  return with_skip_mode(skip_mode, [&](auto mode) {
+    return launch_deep<CIN, decltype(mode)::value>(x, wpk, scale, shift, skip, wskip, scale_s, shift_s, out, D, N, st);
+  });
 }
 
 template <int COUT>
@@ -332,14 +315,9 @@ extern "C" int mvn_v2v_conv3_deep(const void* x, int cin, const void* weight_pac
                                   const void* skip_weight_packed, const float* skip_scale,
                                   const float* skip_shift, void* out, int B, int D, void* stream) {
   using namespace mvn;
-  if (!x || !weight_packed || !scale || !shift || !out) return MVN_ERR_ARG;
-  if (skip_mode != MVN_SKIP_NONE && skip_mode != MVN_SKIP_IDENTITY && skip_mode != MVN_SKIP_POINTWISE)
-    return MVN_ERR_ARG;
-  const bool pw = skip_weight_packed || skip_scale || skip_shift;
-  if (skip_mode == MVN_SKIP_NONE && (skip || pw)) return MVN_ERR_ARG;
-  if (skip_mode == MVN_SKIP_IDENTITY && (!skip || pw)) return MVN_ERR_ARG;
-  if (skip_mode == MVN_SKIP_POINTWISE && (!skip || !skip_weight_packed || !skip_scale || !skip_shift))
-    return MVN_ERR_ARG;
+  const int rc = check_conv3_pointers(x, weight_packed, scale, shift, skip_mode, skip, skip_weight_packed, skip_scale,
+                                      skip_shift, out);
+  if (rc != MVN_OK) return rc;
   if (B < 1 || D < 1 || D > kDeepMaxD || (cin != 64 && cin != 128)) return MVN_ERR_SHAPE;
   if (skip_mode == MVN_SKIP_IDENTITY && skip_cin != 128) return MVN_ERR_SHAPE;
   if (skip_mode == MVN_SKIP_POINTWISE && skip_cin != 64) return MVN_ERR_SHAPE;

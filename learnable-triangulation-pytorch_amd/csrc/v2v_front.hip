@@ -20,7 +20,7 @@
 #include <climits>
 #include <type_traits>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace mvn {
 namespace {
@@ -34,18 +34,6 @@ constexpr int kPass = KS * KS;                                         // (dx, d
 constexpr int kStage = (TX * HY * HZ * 4 + kThreads - 1) / kThreads;   // halo chunks per thread per tile: 14
 // __builtin_amdgcn_sched_group_barrier instruction classes
 constexpr int kSgMfma = 0x008, kSgVmemRead = 0x020, kSgDsRead = 0x100;
-constexpr uint32_t kOob = 0x80000000u;
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(a));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(a >> 32));
-  void* p = reinterpret_cast<void*>((uint64_t(hi) << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(p, 0, int(__builtin_amdgcn_readfirstlane(bytes)), 0x00020000);
-}
 
 // LDS swizzle of a halo voxel's four 16-byte channel chunks: chunk c of a voxel at halo z
 // index hz sits at position c ^ swz(hz).  The A-operand read of one MFMA has lanes
@@ -208,8 +196,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
           for (int m = m_lo; m <= m_hi; ++m) {
             const int xa = XONLY >= 0 ? XONLY : x;
-            acc[xa][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, A[x][hy]),
-                                                                 __builtin_bit_cast(bf16x8_t, Bf[hy - m]), acc[xa][m], 0, 0, 0);
+            acc[xa][m] = mfma(A[x][hy], Bf[hy - m], acc[xa][m]);
           }
           if (la && (!NEXT_ONE || x == 0)) A[x][hy] = ld_a(hb[x], hy);
         }

@@ -28,7 +28,7 @@
 #include <climits>
 #include <type_traits>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace mvn {
 namespace {
@@ -41,17 +41,9 @@ constexpr int kLayerBytes = 2 * kWave * 16;  // packed weights of one layer: [m]
 
 enum : int { kInNcdhwF32 = 0, kInNcdhwBf16 = 1, kInNdhwcBf16 = 2 };
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 struct Frag {                                // one B operand: 8 bf16 of one voxel column
   uint32_t d[4];
 };
-
-__device__ __forceinline__ f32x4_t mfma(const uint4& a, const Frag& b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c,
-                                                 0, 0, 0);
-}
 
 // The 64-voxel chunk at voxel v0 of a frame of S voxels, as loaded: tile t of the lane is voxel
 // v0 + 4c + t, channels 8g .. 8g + 7.  No branches and no waits between the loads: a lane whose

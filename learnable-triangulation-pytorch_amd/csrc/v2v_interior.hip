@@ -33,7 +33,7 @@
 // Pool.  One thread per output voxel and 8 channels: eight 16-byte loads, one 16-byte store.
 #include <climits>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace mvn {
 namespace {
@@ -43,23 +43,6 @@ constexpr int TX = 4, TY = 8, TZ = 16;
 constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2;                 // 6, 10, 18
 constexpr int kWaves = 4, kThreads = kWaves * kWave;
 constexpr int kRows = TY / kWaves;                                   // output y-rows per wave: 2
-constexpr uint32_t kOob = 0x80000000u;
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(a));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(a >> 32));
-  void* p = reinterpret_cast<void*>((uint64_t(hi) << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(p, 0, int(__builtin_amdgcn_readfirstlane(bytes)), 0x00020000);
-}
-
-__device__ __forceinline__ f32x4_t mfma(const uint4& a, const uint4& b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c,
-                                                 0, 0, 0);
-}
 
 // LDS position of 16-byte channel chunk c of a halo voxel at halo z index hz.  Four chunks
 // (64-byte voxels): v2v_res3d's swizzle.  Eight chunks (128-byte voxels): voxel pairs rotate
@@ -324,18 +307,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
         for (int m = 0; m < MT; ++m) {
           float y[4];
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float r = __builtin_fmaf(acc[x][yl][m][i], sc[m][i], sh[m][i]);
-            if constexpr (MODE == MVN_SKIP_IDENTITY) {
-              const uint32_t pair = i < 2 ? sk[yl][m].x : sk[yl][m].y;
-              r = r + __uint_as_float((i & 1) ? (pair & 0xffff0000u) : (pair << 16));
-            } else if constexpr (MODE == MVN_SKIP_POINTWISE) {
-              r = r + __builtin_fmaf(accs[m][i], scs[m][i], shs[m][i]);
-            }
-            y[i] = relu_keep_nan(r);
-          }
-          *reinterpret_cast<uint2*>(out + v * CO + 16 * m + 4 * g) =
-              make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+          for (int i = 0; i < 4; ++i)
+            y[i] = bn_skip_relu<MODE>(acc[x][yl][m], sc[m], sh[m], sk[yl][m], accs[m], scs[m], shs[m], i);
+          *reinterpret_cast<uint2*>(out + v * CO + 16 * m + 4 * g) = pack_bf16x4(y);
         }
       }
     }
@@ -396,17 +370,10 @@ __global__ __launch_bounds__(kThreads) void v2v_upsample2(const uint16_t* __rest
       f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
       acc = mfma(A[0][m], B0, acc);
       acc = mfma(A[1][m], B1, acc);
-      float yv[4];
+      float y[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float u = relu_keep_nan(__builtin_fmaf(acc[i], sc[h][i], sh[h][i]));
-        if constexpr (SKIP) {
-          const uint32_t pair = i < 2 ? sk.x : sk.y;
-          u = u + __uint_as_float((i & 1) ? (pair & 0xffff0000u) : (pair << 16));
-        }
-        yv[i] = u;
-      }
-      *reinterpret_cast<uint2*>(out + o) = make_uint2(pack_bf16x2(yv[0], yv[1]), pack_bf16x2(yv[2], yv[3]));
+      for (int i = 0; i < 4; ++i) y[i] = bn_relu_add<SKIP>(acc, sc[h], sh[h], sk, i);
+      *reinterpret_cast<uint2*>(out + o) = pack_bf16x4(y);
     }
   }
 }
@@ -478,12 +445,9 @@ int launch_wide(const void* x, const void* wpk, const float* scale, const float*
   const auto* sk = static_cast<const uint16_t*>(skip);
   const auto* ws = static_cast<const uint4*>(wskip);
   auto* o = static_cast<uint16_t*>(out);
-  if (skip_mode == MVN_SKIP_NONE)
-    v2v_conv3_wide<CIN, MVN_SKIP_NONE><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V, seg);
-  else if (skip_mode == MVN_SKIP_IDENTITY)
-    v2v_conv3_wide<CIN, MVN_SKIP_IDENTITY><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V, seg);
-  else
-    v2v_conv3_wide<CIN, MVN_SKIP_POINTWISE><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V, seg);
+  with_skip_mode(skip_mode, [&](auto mode) {
+    v2v_conv3_wide<CIN, decltype(mode)::value><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V, seg);
+  });
   return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
 }
 
@@ -503,14 +467,9 @@ extern "C" int mvn_v2v_conv3_wide(const void* x, int cin, const void* weight_pac
                                   const void* skip_weight_packed, const float* skip_scale,
                                   const float* skip_shift, void* out, int B, int V, void* stream) {
   using namespace mvn;
-  if (!x || !weight_packed || !scale || !shift || !out) return MVN_ERR_ARG;
-  if (skip_mode != MVN_SKIP_NONE && skip_mode != MVN_SKIP_IDENTITY && skip_mode != MVN_SKIP_POINTWISE)
-    return MVN_ERR_ARG;
-  const bool pw = skip_weight_packed || skip_scale || skip_shift;
-  if (skip_mode == MVN_SKIP_NONE && (skip || pw)) return MVN_ERR_ARG;
-  if (skip_mode == MVN_SKIP_IDENTITY && (!skip || pw)) return MVN_ERR_ARG;
-  if (skip_mode == MVN_SKIP_POINTWISE && (!skip || !skip_weight_packed || !skip_scale || !skip_shift))
-    return MVN_ERR_ARG;
+  const int rc = check_conv3_pointers(x, weight_packed, scale, shift, skip_mode, skip, skip_weight_packed, skip_scale,
+                                      skip_shift, out);
+  if (rc != MVN_OK) return rc;
   if (B < 1 || !wide_volume_ok(V) || (cin != 32 && cin != 64)) return MVN_ERR_SHAPE;
   if (skip_mode == MVN_SKIP_IDENTITY && skip_cin != 64) return MVN_ERR_SHAPE;
   if (skip_mode == MVN_SKIP_POINTWISE && skip_cin != 32) return MVN_ERR_SHAPE;

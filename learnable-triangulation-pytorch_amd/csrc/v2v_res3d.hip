@@ -35,7 +35,7 @@
 // Arithmetic: 2 * 27 * 32 * 32 * V^3 flop per frame (14.5 GFLOP at V = 64, Cin = 32).
 #include <climits>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace mvn {
 namespace {
@@ -46,23 +46,6 @@ constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2;                 // 6, 10, 1
 constexpr int kWaves = 4, kThreads = kWaves * kWave;
 constexpr int kRows = TY / kWaves;                                   // output y-rows per wave: 2
 constexpr int kWChunks = NTAP * 2 * kWave;                           // 3456 chunks of 16 B: [tap][m][lane]
-constexpr uint32_t kOob = 0x80000000u;
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(a));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(a >> 32));
-  void* p = reinterpret_cast<void*>((uint64_t(hi) << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(p, 0, int(__builtin_amdgcn_readfirstlane(bytes)), 0x00020000);
-}
-
-__device__ __forceinline__ f32x4_t mfma(const uint4& a, const uint4& b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c,
-                                                 0, 0, 0);
-}
 
 // LDS position of 16-byte channel chunk c of a halo voxel at halo z index hz.  Cin = 32 (four
 // chunks, 64-byte voxel pitch): v2v_front's swizzle, which spreads the 16 z-consecutive voxels
@@ -305,18 +288,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
         for (int m = 0; m < 2; ++m) {
           float y[4];
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float r = __builtin_fmaf(acc[x][yl][m][i], sc[m][i], sh[m][i]);
-            if constexpr (MODE == MVN_SKIP_IDENTITY) {
-              const uint32_t pair = i < 2 ? sk[x][yl][m].x : sk[x][yl][m].y;
-              r = r + __uint_as_float((i & 1) ? (pair & 0xffff0000u) : (pair << 16));
-            } else if constexpr (MODE == MVN_SKIP_POINTWISE) {
-              r = r + __builtin_fmaf(accs[m][i], scs[m][i], shs[m][i]);
-            }
-            y[i] = relu_keep_nan(r);
-          }
-          *reinterpret_cast<uint2*>(out + v * CO + 16 * m + 4 * g) =
-              make_uint2(pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]));
+          for (int i = 0; i < 4; ++i)
+            y[i] = bn_skip_relu<MODE>(acc[x][yl][m], sc[m], sh[m], sk[x][yl][m], accs[m], scs[m], shs[m], i);
+          *reinterpret_cast<uint2*>(out + v * CO + 16 * m + 4 * g) = pack_bf16x4(y);
         }
       }
   }
@@ -335,13 +309,8 @@ bool volume_ok(int V) { return V >= 16 && V <= 256 && V % 16 == 0; }
 int check_conv3(const void* x, int cin, const void* wpk, const float* scale, const float* shift, int skip_mode,
                 const void* skip, int skip_cin, const void* wskip, const float* scale_s, const float* shift_s,
                 const void* out, int B, int V) {
-  if (!x || !wpk || !scale || !shift || !out) return MVN_ERR_ARG;
-  if (skip_mode != MVN_SKIP_NONE && skip_mode != MVN_SKIP_IDENTITY && skip_mode != MVN_SKIP_POINTWISE)
-    return MVN_ERR_ARG;
-  const bool pw = wskip || scale_s || shift_s;
-  if (skip_mode == MVN_SKIP_NONE && (skip || pw)) return MVN_ERR_ARG;
-  if (skip_mode == MVN_SKIP_IDENTITY && (!skip || pw)) return MVN_ERR_ARG;
-  if (skip_mode == MVN_SKIP_POINTWISE && (!skip || !wskip || !scale_s || !shift_s)) return MVN_ERR_ARG;
+  const int rc = check_conv3_pointers(x, wpk, scale, shift, skip_mode, skip, wskip, scale_s, shift_s, out);
+  if (rc != MVN_OK) return rc;
   if (B < 1 || !volume_ok(V) || (cin != 16 && cin != 32)) return MVN_ERR_SHAPE;
   if (skip_mode == MVN_SKIP_IDENTITY && skip_cin != 32) return MVN_ERR_SHAPE;
   if (skip_mode == MVN_SKIP_POINTWISE && skip_cin != 16) return MVN_ERR_SHAPE;
@@ -359,12 +328,9 @@ int launch_conv3(const void* x, const void* wpk, const float* scale, const float
   const auto* sk = static_cast<const uint16_t*>(skip);
   const auto* ws = static_cast<const uint4*>(wskip);
   auto* o = static_cast<uint16_t*>(out);
-  if (skip_mode == MVN_SKIP_NONE)
-    v2v_conv3<CIN, MVN_SKIP_NONE><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V);
-  else if (skip_mode == MVN_SKIP_IDENTITY)
-    v2v_conv3<CIN, MVN_SKIP_IDENTITY><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V);
-  else
-    v2v_conv3<CIN, MVN_SKIP_POINTWISE><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V);
+  with_skip_mode(skip_mode, [&](auto mode) {
+    v2v_conv3<CIN, decltype(mode)::value><<<nblk, kThreads, 0, st>>>(in, wp, scale, shift, sk, ws, scale_s, shift_s, o, V);
+  });
   return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
 }
 

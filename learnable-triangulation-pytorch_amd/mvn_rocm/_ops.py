@@ -271,29 +271,44 @@ def _(x, packed, scale_shift, bias3, coords, cuboids, transfer, softmax, multipl
     return x.new_empty((B, J, 3), dtype=torch.float32), x.new_empty(shape, dtype=_CODE_DTYPE[out_dtype])
 
 
-# --------------------------------------------------------------------------- V2V Res3DBlock
-@_op("v2v_conv3")
-def v2v_conv3(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip_mode: int, skip: Optional[Tensor],
+# --------------------------------------------------------------------------- V2V Res3DBlock convs (32, 64, 128 channels)
+def _conv3_op(name: str, cout: int, doc: str):
+    """Register ``mvn_rocm::<name>`` and its fake: one 3x3x3 conv launch with ``cout`` output
+    channels through the C entry point ``mvn_<name>``.  The three widths differ in nothing else."""
+    entry = f"mvn_{name}"
+
+    def conv3(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip_mode: int, skip: Optional[Tensor],
               skip_packed: Optional[Tensor], skip_scale: Optional[Tensor], skip_shift: Optional[Tensor]) -> Tensor:
-    """x (B,V,V,V,cin) bf16, cin 16 | 32 -> (B,V,V,V,32) bf16: relu(bn(conv3d_3(x)) + skip term)
-    (csrc/v2v_res3d.hip); skip (B,V,V,V,32) with MVN_SKIP_IDENTITY, (B,V,V,V,16) and its packed
-    1x1x1 weights, scale and shift with MVN_SKIP_POINTWISE."""
-    _require_gpu(x, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
-    B, V, cin = x.shape[0], x.shape[1], x.shape[4]
-    out = torch.empty((B, V, V, V, 32), dtype=torch.bfloat16, device=x.device)
-    if out.numel() == 0:                  # empty batch: nothing to launch
+        _require_gpu(x, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
+        B, V, cin = x.shape[0], x.shape[1], x.shape[4]
+        out = torch.empty((B, V, V, V, cout), dtype=torch.bfloat16, device=x.device)
+        if out.numel() == 0:                  # empty batch: nothing to launch
+            return out
+        code = getattr(_lib.load(), entry)(
+            x.data_ptr(), cin, packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(skip_mode), _ptr(skip),
+            skip.shape[4] if skip is not None else 0, _ptr(skip_packed), _ptr(skip_scale), _ptr(skip_shift),
+            out.data_ptr(), B, V, _stream(x))
+        _lib.check(code, entry)
         return out
-    code = _lib.load().mvn_v2v_conv3(
-        x.data_ptr(), cin, packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(skip_mode), _ptr(skip),
-        skip.shape[4] if skip is not None else 0, _ptr(skip_packed), _ptr(skip_scale), _ptr(skip_shift),
-        out.data_ptr(), B, V, _stream(x))
-    _lib.check(code, "mvn_v2v_conv3")
-    return out
+
+    conv3.__name__, conv3.__doc__ = name, doc
+    op = _op(name)(conv3)
+
+    @op.register_fake
+    def _(x, packed, scale, shift, skip_mode, skip, skip_packed, skip_scale, skip_shift):
+        return x.new_empty((*x.shape[:4], cout), dtype=torch.bfloat16)
+    return op
 
 
-@v2v_conv3.register_fake
-def _(x, packed, scale, shift, skip_mode, skip, skip_packed, skip_scale, skip_shift):
-    return x.new_empty((*x.shape[:4], 32), dtype=torch.bfloat16)
+v2v_conv3 = _conv3_op("v2v_conv3", 32, """x (B,V,V,V,cin) bf16, cin 16 | 32 -> (B,V,V,V,32) bf16:
+    relu(bn(conv3d_3(x)) + skip term) (csrc/v2v_res3d.hip); skip (B,V,V,V,32) with MVN_SKIP_IDENTITY,
+    (B,V,V,V,16) and its packed 1x1x1 weights, scale and shift with MVN_SKIP_POINTWISE.""")
+v2v_conv3_wide = _conv3_op("v2v_conv3_wide", 64, """x (B,V,V,V,cin) bf16, cin 32 | 64 -> (B,V,V,V,64) bf16:
+    relu(bn(conv3d_3(x)) + skip term) (csrc/v2v_interior.hip); skip (B,V,V,V,64) with MVN_SKIP_IDENTITY,
+    (B,V,V,V,32) and its packed 1x1x1 weights, scale and shift with MVN_SKIP_POINTWISE.""")
+v2v_conv3_deep = _conv3_op("v2v_conv3_deep", 128, """x (B,D,D,D,cin) bf16, cin 64 | 128, any D in [1, 64] ->
+    (B,D,D,D,128) bf16: relu(bn(conv3d_3(x)) + skip term) (csrc/v2v_deep.hip); skip (B,D,D,D,128) with
+    MVN_SKIP_IDENTITY, (B,D,D,D,64) and its packed 1x1x1 weights, scale and shift with MVN_SKIP_POINTWISE.""")
 
 
 @_op("v2v_res3d")
@@ -345,31 +360,6 @@ def _(x):
     return x.new_empty((B, V // 2, V // 2, V // 2, C), dtype=torch.bfloat16)
 
 
-@_op("v2v_conv3_wide")
-def v2v_conv3_wide(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip_mode: int, skip: Optional[Tensor],
-                   skip_packed: Optional[Tensor], skip_scale: Optional[Tensor],
-                   skip_shift: Optional[Tensor]) -> Tensor:
-    """x (B,V,V,V,cin) bf16, cin 32 | 64 -> (B,V,V,V,64) bf16: relu(bn(conv3d_3(x)) + skip term)
-    (csrc/v2v_interior.hip); skip (B,V,V,V,64) with MVN_SKIP_IDENTITY, (B,V,V,V,32) and its packed
-    1x1x1 weights, scale and shift with MVN_SKIP_POINTWISE."""
-    _require_gpu(x, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
-    B, V, cin = x.shape[0], x.shape[1], x.shape[4]
-    out = torch.empty((B, V, V, V, 64), dtype=torch.bfloat16, device=x.device)
-    if out.numel() == 0:                  # empty batch: nothing to launch
-        return out
-    code = _lib.load().mvn_v2v_conv3_wide(
-        x.data_ptr(), cin, packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(skip_mode), _ptr(skip),
-        skip.shape[4] if skip is not None else 0, _ptr(skip_packed), _ptr(skip_scale), _ptr(skip_shift),
-        out.data_ptr(), B, V, _stream(x))
-    _lib.check(code, "mvn_v2v_conv3_wide")
-    return out
-
-
-@v2v_conv3_wide.register_fake
-def _(x, packed, scale, shift, skip_mode, skip, skip_packed, skip_scale, skip_shift):
-    return x.new_empty((*x.shape[:4], 64), dtype=torch.bfloat16)
-
-
 @_op("v2v_upsample2")
 def v2v_upsample2(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip: Optional[Tensor]) -> Tensor:
     """x (B,V,V,V,64) bf16 -> (B,2V,2V,2V,32) bf16: relu(bn(conv_transpose3d_2(x))) + skip
@@ -392,31 +382,6 @@ def _(x, packed, scale, shift, skip):
 
 
 # --------------------------------------------------------------------------- V2V 128-channel levels
-@_op("v2v_conv3_deep")
-def v2v_conv3_deep(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip_mode: int, skip: Optional[Tensor],
-                   skip_packed: Optional[Tensor], skip_scale: Optional[Tensor],
-                   skip_shift: Optional[Tensor]) -> Tensor:
-    """x (B,D,D,D,cin) bf16, cin 64 | 128, any D in [1, 64] -> (B,D,D,D,128) bf16:
-    relu(bn(conv3d_3(x)) + skip term) (csrc/v2v_deep.hip); skip (B,D,D,D,128) with MVN_SKIP_IDENTITY,
-    (B,D,D,D,64) and its packed 1x1x1 weights, scale and shift with MVN_SKIP_POINTWISE."""
-    _require_gpu(x, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
-    B, D, cin = x.shape[0], x.shape[1], x.shape[4]
-    out = torch.empty((B, D, D, D, 128), dtype=torch.bfloat16, device=x.device)
-    if out.numel() == 0:                  # empty batch: nothing to launch
-        return out
-    code = _lib.load().mvn_v2v_conv3_deep(
-        x.data_ptr(), cin, packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(skip_mode), _ptr(skip),
-        skip.shape[4] if skip is not None else 0, _ptr(skip_packed), _ptr(skip_scale), _ptr(skip_shift),
-        out.data_ptr(), B, D, _stream(x))
-    _lib.check(code, "mvn_v2v_conv3_deep")
-    return out
-
-
-@v2v_conv3_deep.register_fake
-def _(x, packed, scale, shift, skip_mode, skip, skip_packed, skip_scale, skip_shift):
-    return x.new_empty((*x.shape[:4], 128), dtype=torch.bfloat16)
-
-
 @_op("v2v_upsample2_deep")
 def v2v_upsample2_deep(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip: Optional[Tensor]) -> Tensor:
     """x (B,D,D,D,128) bf16 -> (B,2D,2D,2D,cout) bf16, cout = scale.numel() (64 | 128):

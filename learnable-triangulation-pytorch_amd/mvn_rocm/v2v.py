@@ -25,7 +25,7 @@ the 128-channel levels below run on kernels as well, at any extent from 64 down 
 """
 from __future__ import annotations
 
-from typing import NamedTuple, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -37,26 +37,51 @@ from .op import _dtype_code, aggregation_code, unproject_inputs
 CIN, COUT, KS = 32, 16, 7
 
 
+def _f64(t):
+    return t.detach().to(torch.float64).cpu()
+
+
+def _bn_fold(bias, gamma, beta, mean, var, eps, channels):
+    """float64 (scale, shift) of an eval-mode BatchNorm behind a conv with ``bias`` (or None):
+    bn(conv(x) + bias) = conv(x) * scale + shift with scale = gamma / (var + eps) ** 0.5 and
+    shift = (bias - mean) * scale + beta.  Every fold of this module goes through here."""
+    s = _f64(gamma) / torch.sqrt(_f64(var) + eps)
+    b = _f64(bias) if bias is not None else torch.zeros(channels, dtype=torch.float64)
+    return s, (b - _f64(mean)) * s + _f64(beta)
+
+
+def _pack_mfma_a(w):
+    """(..., R, K) float64, R a multiple of 16 and K of 32 -> (..., K / 32, R / 16, 64, 8) bf16, the
+    A fragments of v_mfma_f32_16x16x32_bf16 as every V2V kernel reads them:
+    [kp][m][lane][j] = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j].  Each ``pack_*`` below is
+    a reshape of its weight into rows and K-slots, this function, and at most a dropped ``kp``."""
+    *lead, R, K = w.shape
+    n = len(lead)
+    p = w.reshape(*lead, R // 16, 16, K // 32, 4, 8)                                 # [m][lane & 15][kp][lane >> 4][j]
+    p = p.permute(*range(n), n + 2, n, n + 3, n + 1, n + 4)                          # [kp][m][lane >> 4][lane & 15][j]
+    return p.reshape(*lead, K // 32, R // 16, 64, 8).to(torch.float32).to(torch.bfloat16).contiguous()
+
+
+def _pad_k(w):
+    """The last axis zero-padded to a multiple of 32 K-slots."""
+    return nn.functional.pad(w, (0, -w.shape[-1] % 32))
+
+
 def fold_basic3d_block(weight, bias, bn_weight, bn_bias, running_mean, running_var, eps=1e-5, device="cuda"):
     """Eval-mode Basic3DBlock parameters -> (packed bf16 weights, scale, shift) on ``device``.
 
-    y = relu(bn(conv(x) + bias)) = relu(conv(x) * s + ((bias - mean) * s + beta)),
-    s = gamma / sqrt(var + eps), folded in float64.  The weights are rounded to bf16 (the
+    y = relu(bn(conv(x) + bias)) = relu(conv(x) * s + ((bias - mean) * s + beta)), s the BatchNorm's
+    scale, folded in float64 (``_bn_fold``).  The weights are rounded to bf16 (the
     kernel's MFMA operand type) and packed [tap][lane][8] as mvn_v2v_front expects."""
-    w = weight.detach().to(torch.float64).cpu()
+    w = _f64(weight)
     if tuple(w.shape) != (COUT, CIN, KS, KS, KS):
         raise RuntimeError(f"expected a ({COUT}, {CIN}, 7, 7, 7) Conv3d weight, got {tuple(w.shape)}")
-    s = bn_weight.detach().double().cpu() / torch.sqrt(running_var.detach().double().cpu() + eps)
-    b = bias.detach().double().cpu() if bias is not None else torch.zeros(COUT, dtype=torch.float64)
-    shift = (b - running_mean.detach().double().cpu()) * s + bn_bias.detach().double().cpu()
-    wt = w.reshape(COUT, CIN, KS ** 3).permute(2, 0, 1)                 # [tap][cout][cin]
-    lane = torch.arange(64)
-    cout, kblk = lane % 16, lane // 16
-    cin = kblk.view(64, 1) * 8 + torch.arange(8).view(1, 8)            # [lane][j]
-    packed = wt[:, cout.view(64, 1).expand(64, 8), cin]                 # [tap][lane][j]
-    packed = packed.to(torch.float32).to(torch.bfloat16).contiguous()
+    s, shift = _bn_fold(bias, bn_weight, bn_bias, running_mean, running_var, eps, COUT)
+    packed = _pack_mfma_a(w.reshape(COUT, CIN, KS ** 3).permute(2, 0, 1))[:, 0, 0]    # [tap][lane][j]
     dev = torch.device(device)
     return packed.to(dev), s.float().to(dev), shift.float().to(dev)
+
+
 
 
 def v2v_front(vol_cl, packed, scale, shift, out_dtype=torch.float32):
@@ -250,17 +275,19 @@ def head_kslot(layer):
     return 16 * (j // 4) + 4 * g + (j % 4)
 
 
-def _fold_bn(conv, bn, what):
-    """(f64 weight (32, 32), f64 scale, f64 shift) of an eval-mode Conv3d(32, 32, 1) + BatchNorm3d."""
-    w = conv.weight.detach().to(torch.float64).cpu()
-    if tuple(w.shape) != (HEAD_C, HEAD_C, 1, 1, 1):
-        raise RuntimeError(f"{what}: expected a ({HEAD_C}, {HEAD_C}, 1, 1, 1) Conv3d weight, got {tuple(w.shape)}")
-    if bn.running_mean is None or tuple(bn.running_mean.shape) != (HEAD_C,):
-        raise RuntimeError(f"{what}: expected a BatchNorm3d({HEAD_C}) with running statistics")
-    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
-    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(HEAD_C, dtype=torch.float64)
-    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
-    return w.reshape(HEAD_C, HEAD_C), s, shift
+def _fold_conv_bn(conv, bn, what, ks, cout, cins):
+    """(f64 weight, f64 scale, f64 shift) of an eval-mode Conv3d(cins -> cout, ks) + BatchNorm3d(cout)."""
+    w = getattr(conv, "weight", None)
+    want = " | ".join(map(str, cins))
+    if not isinstance(conv, nn.Conv3d) or w.shape[0] != cout or w.shape[1] not in cins or tuple(w.shape[2:]) != (ks,) * 3:
+        got = tuple(w.shape) if w is not None else type(conv).__name__
+        raise RuntimeError(f"{what}: expected a ({cout}, {want}, {ks}, {ks}, {ks}) Conv3d weight, got {got}")
+    pad = (ks - 1) // 2
+    if tuple(conv.stride) != (1, 1, 1) or tuple(conv.padding) != (pad,) * 3 or tuple(conv.dilation) != (1, 1, 1):
+        raise RuntimeError(f"{what}: expected stride 1, padding {pad} and no dilation")
+    if bn.running_mean is None or tuple(bn.running_mean.shape) != (cout,):
+        raise RuntimeError(f"{what}: expected a BatchNorm3d({cout}) with running statistics")
+    return (_f64(w), *_bn_fold(conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, cout))
 
 
 def fold_v2v_head(block1, block2, output_conv, device="cuda"):
@@ -268,27 +295,24 @@ def fold_v2v_head(block1, block2, output_conv, device="cuda"):
     BN) and a ``Conv3d(32, J, 1)`` -> (packed bf16 weights, scale_shift (2, 2, 32) f32, bias3 (J,)
     f32) on ``device``.  BN and the conv bias are folded in float64 as in ``fold_basic3d_block``;
     the weights are rounded to bf16 and packed [layer][m][lane][8] as mvn_v2v_head expects."""
-    w1, s1, t1 = _fold_bn(block1.block[0], block1.block[1], "block1")
-    w2, s2, t2 = _fold_bn(block2.block[0], block2.block[1], "block2")
-    w3 = output_conv.weight.detach().to(torch.float64).cpu()
+    w1, s1, t1 = _fold_conv_bn(block1.block[0], block1.block[1], "block1", 1, HEAD_C, (HEAD_C,))
+    w2, s2, t2 = _fold_conv_bn(block2.block[0], block2.block[1], "block2", 1, HEAD_C, (HEAD_C,))
+    w3 = _f64(output_conv.weight)
     J = w3.shape[0]
     if w3.dim() != 5 or tuple(w3.shape[1:]) != (HEAD_C, 1, 1, 1) or not 1 <= J <= HEAD_C:
         raise RuntimeError(f"output_conv: expected a (J <= {HEAD_C}, {HEAD_C}, 1, 1, 1) Conv3d weight, "
                            f"got {tuple(w3.shape)}")
     w3p = torch.zeros(HEAD_C, HEAD_C, dtype=torch.float64)
     w3p[:J] = w3.reshape(J, HEAD_C)
-    b3 = output_conv.bias.detach().double().cpu() if output_conv.bias is not None else torch.zeros(J, dtype=torch.float64)
-    lane = torch.arange(64)
-    row, k = lane % 16, (lane // 16).view(64, 1) * 8 + torch.arange(8).view(1, 8)    # [lane], [lane][j]
-    packed = torch.empty(3, 2, 64, 8, dtype=torch.float64)
-    for l, w in enumerate((w1, w2, w3p)):
-        cin = head_kslot(l)[k]                                                       # [lane][j]
-        for m in range(2):
-            packed[l, m] = w[(16 * m + row).view(64, 1).expand(64, 8), cin]
-    packed = packed.to(torch.float32).to(torch.bfloat16).contiguous()
+    b3 = _f64(output_conv.bias) if output_conv.bias is not None else torch.zeros(J, dtype=torch.float64)
+    # K-slot k of layer l reads input channel head_kslot(l)[k]
+    layers = (w1.reshape(HEAD_C, HEAD_C), w2.reshape(HEAD_C, HEAD_C), w3p)
+    packed = _pack_mfma_a(torch.stack([w[:, head_kslot(l)] for l, w in enumerate(layers)]))[:, 0]
     scale_shift = torch.stack([torch.stack([s1, t1]), torch.stack([s2, t2])]).float().contiguous()
     dev = torch.device(device)
     return packed.to(dev), scale_shift.to(dev), b3.float().to(dev)
+
+
 
 
 def _head_input(what, x, packed, scale_shift, bias3, channels_last):
@@ -384,11 +408,22 @@ def v2v_trunk(v2v_model, x):
     return v2v_model.back_layers[0](x)
 
 
-# --------------------------------------------------------------------------- full-resolution Res3DBlocks
-# Res3DBlock (mvn/models/v2v.py:20-42) at the full resolution — front_layers[1..3],
-# encoder_decoder.skip_res1, back_layers[0] — as two launches of one 3x3x3 MFMA kernel
-# (csrc/v2v_res3d.hip) on channels-last bf16 volumes.
+# --------------------------------------------------------------------------- Res3DBlocks and upsamples
+# Res3DBlock (mvn/models/v2v.py:20-42) and Upsample3DBlock (:53-65) on channels-last bf16 volumes at
+# the three channel widths of the V2V, each a 3x3x3 MFMA kernel of its own:
+#   32   full resolution: front_layers[1..3], encoder_decoder.skip_res1, back_layers[0]
+#        (csrc/v2v_res3d.hip)
+#   64   first pooled level: encoder_pool1, encoder_res1, skip_res2, decoder_res1 and
+#        decoder_upsample1 with the last ``+ skip_x1`` (csrc/v2v_interior.hip)
+#   128  encoder_pool2 ... decoder_upsample2, at any extent D in [1, 64] (csrc/v2v_deep.hip,
+#        DESIGN.md §4.14)
+# One implementation of the folds, checks and calls serves all three through a ``_Level`` record;
+# the public functions and modules of each width bind it.
 RES_C = 32
+WIDE_C = 64
+UP_CIN, UP_COUT = 64, 32
+DEEP_C = 128
+DEEP_MAX_D = 64
 SKIP_NONE, SKIP_IDENTITY, SKIP_POINTWISE = _lib.MVN_SKIP_NONE, _lib.MVN_SKIP_IDENTITY, _lib.MVN_SKIP_POINTWISE
 
 
@@ -406,92 +441,279 @@ class Res3DParams(NamedTuple):
     skip_shift: Optional[torch.Tensor] = None
 
 
-def _mfma_a_rows():
-    lane = torch.arange(64)
-    return lane % 16, (lane // 16).view(64, 1) * 8 + torch.arange(8).view(1, 8)      # row [lane], K-slot [lane][j]
+class UpsampleParams(NamedTuple):
+    """What ``fold_upsample_block`` returns: packed bf16 weights and f32 scale / shift."""
+    packed: torch.Tensor
+    scale: torch.Tensor
+    shift: torch.Tensor
+
+
+def _pack_taps(w):
+    """(cout, cin, 3, 3, 3) float64 -> (27, K / 32, cout / 16, 64, 8) bf16, K = cin zero-padded to
+    a multiple of 32, tap = (dx*3 + dy)*3 + dz."""
+    cout, cin = w.shape[:2]
+    return _pack_mfma_a(_pad_k(w.reshape(cout, cin, 27).permute(2, 0, 1)))            # rows cout, K-slots cin
 
 
 def pack_conv3_weight(w):
     """(32, cin, 3, 3, 3) float64 -> (27, 2, 64, 8) bf16 as mvn_v2v_conv3 reads it:
     [tap = (dx*3 + dy)*3 + dz][m][lane][j] = w[16 m + (lane & 15)][8 (lane >> 4) + j][dx][dy][dz],
     zero where 8 (lane >> 4) + j >= cin (cin = 16: K zero-padded)."""
-    cin = w.shape[1]
-    wt = torch.zeros(27, RES_C, 32, dtype=torch.float64)
-    wt[:, :, :cin] = w.reshape(RES_C, cin, 27).permute(2, 0, 1)                     # [tap][cout][cin]
-    row, k = _mfma_a_rows()
-    packed = torch.stack([wt[:, (16 * m + row).view(64, 1).expand(64, 8), k] for m in range(2)], dim=1)
-    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+    return _pack_taps(w)[:, 0]
 
 
 def pack_pointwise_skip_weight(w):
     """(32, 16) float64 -> (2, 64, 8) bf16: [m][lane][j] = w[16 m + (lane & 15)][8 (lane >> 4) + j],
     zero where 8 (lane >> 4) + j >= 16."""
-    wt = torch.zeros(RES_C, 32, dtype=torch.float64)
-    wt[:, :w.shape[1]] = w
-    row, k = _mfma_a_rows()
-    packed = torch.stack([wt[(16 * m + row).view(64, 1).expand(64, 8), k] for m in range(2)])
-    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
+    return _pack_mfma_a(_pad_k(w))[0]
 
 
-def _fold_conv_bn(conv, bn, what, ks):
-    """(f64 weight, f64 scale, f64 shift) of an eval-mode Conv3d(16 | 32 -> 32, ks) + BatchNorm3d(32)."""
-    w = conv.weight.detach().to(torch.float64).cpu()
-    if w.dim() != 5 or w.shape[0] != RES_C or w.shape[1] not in (16, 32) or tuple(w.shape[2:]) != (ks,) * 3:
-        raise RuntimeError(f"{what}: expected a ({RES_C}, 16 | 32, {ks}, {ks}, {ks}) Conv3d weight, got {tuple(w.shape)}")
-    pad = (ks - 1) // 2
-    if tuple(conv.stride) != (1, 1, 1) or tuple(conv.padding) != (pad,) * 3 or tuple(conv.dilation) != (1, 1, 1):
-        raise RuntimeError(f"{what}: expected stride 1, padding {pad} and no dilation")
-    if bn.running_mean is None or tuple(bn.running_mean.shape) != (RES_C,):
-        raise RuntimeError(f"{what}: expected a BatchNorm3d({RES_C}) with running statistics")
-    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
-    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(RES_C, dtype=torch.float64)
-    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
-    return w, s, shift
+def pack_conv3_wide_weight(w):
+    """(64, cin, 3, 3, 3) float64, cin 32 | 64 -> (27, cin / 32, 4, 64, 8) bf16 as mvn_v2v_conv3_wide
+    reads it: [tap = (dx*3 + dy)*3 + dz][kp][m][lane][j]
+    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]."""
+    return _pack_taps(w)
 
 
+def pack_pointwise_skip_wide_weight(w):
+    """(64, 32) float64 -> (4, 64, 8) bf16: [m][lane][j] = w[16 m + (lane & 15)][8 (lane >> 4) + j]."""
+    return _pack_mfma_a(w)[0]
+
+
+def pack_conv3_deep_weight(w):
+    """(128, cin, 3, 3, 3) float64, cin 64 | 128 -> (27, cin / 32, 8, 64, 8) bf16 as mvn_v2v_conv3_deep
+    reads it: [tap = (dx*3 + dy)*3 + dz][kp][m][lane][j]
+    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]."""
+    return _pack_taps(w)
+
+
+def pack_pointwise_skip_deep_weight(w):
+    """(128, 64) float64 -> (2, 8, 64, 8) bf16: [kp][m][lane][j]
+    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j]."""
+    return _pack_mfma_a(w)
+
+
+def pack_upsample_weight(w):
+    """(64, 32, 2, 2, 2) float64 ConvTranspose3d weight -> (2, 16, 64, 8) bf16 as mvn_v2v_upsample2
+    reads it: [kp][m][lane][j] = w[32 kp + 8 (lane >> 4) + j][16 (m & 1) + (lane & 15)][dx][dy][dz]
+    with (dx*2 + dy)*2 + dz = m >> 1."""
+    return pack_upsample_deep_weight(w)
+
+
+def pack_upsample_deep_weight(w):
+    """(128, cout, 2, 2, 2) float64 ConvTranspose3d weight, cout 64 | 128 -> (4, 8 cout / 16, 64, 8)
+    bf16 as mvn_v2v_upsample2_deep reads it, with H = cout / 16 channel tiles per offset:
+    [kp][m][lane][j] = w[32 kp + 8 (lane >> 4) + j][16 (m % H) + (lane & 15)][dx][dy][dz]
+    with (dx*2 + dy)*2 + dz = m // H."""
+    cin, cout = w.shape[:2]
+    return _pack_mfma_a(w.reshape(cin, cout, 8).permute(2, 1, 0).reshape(8 * cout, cin))   # rows [offset][cout]
+
+
+class _Level(NamedTuple):
+    """One channel width of the Res3DBlock and upsample kernels: everything in which the folds,
+    checks and calls of the three widths differ."""
+    cout: int                  # a conv's output channels; it takes cout // 2 | cout, a pointwise skip cout // 2
+    ax: str                    # the extent's letter in messages
+    step: int                  # the extent is a multiple of ``step`` in [step, vmax]
+    vmax: int
+    conv_shape: dict           # a conv's input channels -> the shape of its packed weights
+    skip_shape: tuple          # the shape of the packed pointwise-skip weights
+    pack: Callable             # the packers of the two
+    pack_skip: Callable
+    op: str                    # the conv's custom op in ``_ops``, also its public name
+    fold: str                  # the fold that messages cite
+    up_couts: tuple = ()       # the upsample from this width: its output channels, op and fold
+    up_op: str = ""
+    up_fold: str = ""
+
+    @property
+    def cins(self):
+        return (self.cout // 2, self.cout)
+
+
+_RES = _Level(RES_C, "V", 16, 256, {16: (27, 2, 64, 8), 32: (27, 2, 64, 8)}, (2, 64, 8),
+              pack_conv3_weight, pack_pointwise_skip_weight, "v2v_conv3", "fold_res3d_block")
+_WIDE = _Level(WIDE_C, "V", 16, 128, {32: (27, 1, 4, 64, 8), 64: (27, 2, 4, 64, 8)}, (4, 64, 8),
+               pack_conv3_wide_weight, pack_pointwise_skip_wide_weight, "v2v_conv3_wide", "fold_res3d_block_wide",
+               (UP_COUT,), "v2v_upsample2", "fold_upsample_block")
+_DEEP = _Level(DEEP_C, "D", 1, DEEP_MAX_D, {64: (27, 2, 8, 64, 8), 128: (27, 4, 8, 64, 8)}, (2, 8, 64, 8),
+               pack_conv3_deep_weight, pack_pointwise_skip_deep_weight, "v2v_conv3_deep", "fold_res3d_block_deep",
+               (64, 128), "v2v_upsample2_deep", "fold_upsample_block_deep")
+
+
+def _one_of(values):
+    return " | ".join(map(str, values))
+
+
+def _fold_res3d(lv, block, device):
+    """``fold_res3d_block*``: the two 3x3x3 convs and the 1x1x1 ``skip_con`` of a Res3DBlock with
+    ``lv``'s channels, BN and biases folded in float64, as ``Res3DParams`` on ``device``."""
+    rb, sk = getattr(block, "res_branch", None), getattr(block, "skip_con", None)
+    if rb is None or sk is None or len(rb) != 5 or len(sk) not in (0, 2):
+        raise RuntimeError("expected a module with Res3DBlock's res_branch of 5 modules and skip_con of 0 or 2, got "
+                           + type(block).__name__)
+    C, dev = lv.cout, torch.device(device)
+    w1, s1, t1 = _fold_conv_bn(rb[0], rb[1], "res_branch[0]", 3, C, lv.cins)
+    w2, s2, t2 = _fold_conv_bn(rb[3], rb[4], "res_branch[3]", 3, C, (C,))
+    cin = w1.shape[1]
+    skip = (None, None, None)
+    if len(sk) == 2:
+        ws, ss, ts = _fold_conv_bn(sk[0], sk[1], "skip_con[0]", 1, C, (C // 2,))
+        if cin != C // 2:
+            raise RuntimeError(f"a block with a 1x1x1 skip_con must take {C // 2} channels, got {cin}")
+        skip = (lv.pack_skip(ws.reshape(C, C // 2)).to(dev), ss.float().to(dev), ts.float().to(dev))
+    elif cin != C:
+        raise RuntimeError(f"a block with an empty skip_con must take {C} channels, got {cin}")
+    return Res3DParams(lv.pack(w1).to(dev), s1.float().to(dev), t1.float().to(dev),
+                       lv.pack(w2).to(dev), s2.float().to(dev), t2.float().to(dev), *skip)
+
+
+def _fold_upsample(lv, block, device):
+    """``fold_upsample_block*``: the ConvTranspose3d(lv.cout, lv.up_couts, 2, stride 2) and the
+    BatchNorm3d of an Upsample3DBlock, folded in float64, as ``UpsampleParams`` on ``device``."""
+    seq = getattr(block, "block", None)
+    if seq is None or len(seq) != 3 or not isinstance(seq[0], nn.ConvTranspose3d):
+        raise RuntimeError("expected block = [ConvTranspose3d, BatchNorm3d, ReLU]")
+    conv, bn = seq[0], seq[1]
+    w = _f64(conv.weight)
+    if w.dim() != 5 or w.shape[0] != lv.cout or w.shape[1] not in lv.up_couts or tuple(w.shape[2:]) != (2, 2, 2):
+        raise RuntimeError(f"block[0]: expected a ({lv.cout}, {_one_of(lv.up_couts)}, 2, 2, 2) ConvTranspose3d weight, "
+                           f"got {tuple(w.shape)}")
+    cout = w.shape[1]
+    if (tuple(conv.stride) != (2, 2, 2) or tuple(conv.padding) != (0, 0, 0) or tuple(conv.output_padding) != (0, 0, 0)
+            or tuple(conv.dilation) != (1, 1, 1) or conv.groups != 1):
+        raise RuntimeError("block[0]: expected stride 2, no padding, no output padding, no dilation, one group")
+    if bn.running_mean is None or tuple(bn.running_mean.shape) != (cout,):
+        raise RuntimeError(f"block[1]: expected a BatchNorm3d({cout}) with running statistics")
+    s, shift = _bn_fold(conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, cout)
+    dev = torch.device(device)
+    return UpsampleParams(pack_upsample_deep_weight(w).to(dev), s.float().to(dev), shift.float().to(dev))
+
+
+def _volume(lv, what, x, name, channels, vmax=None):
+    """Checked contiguous (B, V, V, V, C) bf16 volume of ``lv``'s kernels, C one of ``channels``."""
+    a, vmax = lv.ax, vmax or lv.vmax
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"{what}: {name} must be bfloat16, got {x.dtype}")
+    s = x.shape                                                 # one torch.Size per check: this runs per launch
+    if len(s) != 5 or s[4] not in channels or not s[1] == s[2] == s[3]:
+        raise RuntimeError(f"{what}: {name} must be (B, {a}, {a}, {a}, {_one_of(channels)}), got {tuple(s)}")
+    V = s[1]
+    if V % lv.step != 0 or not lv.step <= V <= vmax:
+        rule = f"in [1, {vmax}]" if lv.step == 1 else f"a multiple of {lv.step} in [{lv.step}, {vmax}]"
+        raise RuntimeError(f"{what}: {name}: {a} must be {rule}, got {V}")
+    return x.contiguous()
+
+
+def _folded(what, packed, scale, shift, shape, channels, fold):
+    """Checked contiguous (packed weights, scale, shift) as ``fold`` returns them."""
+    if (packed.shape != shape or packed.dtype != torch.bfloat16 or scale.shape != (channels,) or shift.shape != (channels,)
+            or scale.dtype != torch.float32 or shift.dtype != torch.float32):
+        raise RuntimeError(f"{what}: packed weights {shape}, scale and shift ({channels},) must be what {fold} returns")
+    return packed.contiguous(), scale.contiguous(), shift.contiguous()
+
+
+def _conv3(lv, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift):
+    """``v2v_conv3*``: the checks of one conv launch and the call of ``lv.op``."""
+    from . import _ops
+    what, C = lv.op, lv.cout
+    _inference_only(what, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift,
+                    instead="the model's own Res3DBlock, which autograd records")
+    x = _volume(lv, what, x_cl, "x_cl", lv.cins)
+    packed, scale, shift = _folded(what, packed, scale, shift, lv.conv_shape[x.shape[4]], C, lv.fold)
+    pw = (skip_packed, skip_scale, skip_shift)
+    if skip is None:
+        if any(t is not None for t in pw):
+            raise RuntimeError(f"{what}: skip weights without a skip volume")
+        mode = SKIP_NONE
+    else:
+        mode = SKIP_POINTWISE if skip_packed is not None else SKIP_IDENTITY
+        skip = _volume(lv, what, skip, "skip", (C // 2,) if mode == SKIP_POINTWISE else (C,))
+        if skip.shape[:4] != x.shape[:4]:
+            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)}")
+        if mode == SKIP_POINTWISE:
+            if skip_scale is None or skip_shift is None:
+                raise RuntimeError(f"{what}: a pointwise skip needs skip_packed, skip_scale and skip_shift")
+            pw = _folded(what, skip_packed, skip_scale, skip_shift, lv.skip_shape, C, lv.fold)
+        elif any(t is not None for t in pw):
+            raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
+    return _ops.call(getattr(_ops, lv.op), x, packed, scale, shift, mode, skip, *pw)
+
+
+def _res3d_two_launches(lv, what, x_cl, params):
+    """``res3d_block_wide`` / ``_deep``: conv1, then conv2 with the block's input as its skip."""
+    p = Res3DParams(*params)
+    _inference_only(what, x_cl, *p, instead="the model's own Res3DBlock, which autograd records")
+    pointwise = p.skip_packed is not None
+    x = _volume(lv, what, x_cl, "x_cl", (lv.cout // 2,) if pointwise else (lv.cout,))
+    h = _conv3(lv, x, p.packed1, p.scale1, p.shift1, None, None, None, None)
+    if not pointwise and (p.skip_scale is not None or p.skip_shift is not None):
+        raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
+    return _conv3(lv, h, p.packed2, p.scale2, p.shift2, x, p.skip_packed, p.skip_scale, p.skip_shift)
+
+
+def _upsample2_add(lv, what, x_cl, params, skip):
+    """``upsample2_add*``: the checks of one upsample launch and the call of ``lv.up_op``."""
+    from . import _ops
+    p = UpsampleParams(*params)
+    _inference_only(what, x_cl, *p, skip, instead="the model's own Upsample3DBlock, which autograd records")
+    x = _volume(lv, what, x_cl, "x_cl", (lv.cout,))
+    cout = p.scale.shape[0] if p.scale.dim() == 1 else -1
+    if cout not in lv.up_couts:
+        raise RuntimeError(f"{what}: scale and shift must be ({_one_of(lv.up_couts)},), got {tuple(p.scale.shape)}")
+    packed, scale, shift = _folded(what, p.packed, p.scale, p.shift, (lv.cout // 32, cout // 2, 64, 8), cout, lv.up_fold)
+    if skip is not None:
+        skip = _volume(lv, what, skip, "skip", (cout,), vmax=2 * lv.vmax)
+        B, V = x.shape[:2]
+        if skip.shape[:4] != (B, 2 * V, 2 * V, 2 * V):
+            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)} upsampled")
+    return _ops.call(getattr(_ops, lv.up_op), x, packed, scale, shift, skip)
+
+
+class _Res3DBlockCL(nn.Module):
+    """Base of the ``Res3DBlock*CL`` modules: the ``Res3DParams`` as buffers of their names;
+    a subclass sets its fold and its forward."""
+    _fold = None
+
+    def __init__(self, params):
+        super().__init__()
+        for name, t in zip(Res3DParams._fields, Res3DParams(*params)):
+            self.register_buffer(name, t)
+
+    @classmethod
+    def from_reference(cls, block, device="cuda"):
+        return cls(cls._fold(block, device=device))
+
+    @property
+    def params(self):
+        return Res3DParams(*(getattr(self, name) for name in Res3DParams._fields))
+
+
+class _Upsample3DBlockCL(nn.Module):
+    """Base of the ``Upsample3DBlock*CL`` modules: the ``UpsampleParams`` as buffers of their names."""
+    _fold = None
+
+    def __init__(self, params):
+        super().__init__()
+        for name, t in zip(UpsampleParams._fields, UpsampleParams(*params)):
+            self.register_buffer(name, t)
+
+    @classmethod
+    def from_reference(cls, block, device="cuda"):
+        return cls(cls._fold(block, device=device))
+
+    @property
+    def params(self):
+        return UpsampleParams(self.packed, self.scale, self.shift)
+
+
+# ---- 32 channels, full resolution
 def fold_res3d_block(block, device="cuda"):
     """An eval-mode module with Res3DBlock's attributes (``res_branch[0..4]`` = conv, BN, ReLU,
     conv, BN; ``skip_con`` empty or [conv 1x1x1, BN]) with 16 | 32 -> 32 channels -> ``Res3DParams``
     on ``device``.  BN and the conv biases are folded in float64 as in ``fold_basic3d_block``; the
     weights are rounded to bf16 and packed as mvn_v2v_conv3 expects (``pack_conv3_weight``)."""
-    rb, sk = block.res_branch, block.skip_con
-    if len(rb) != 5 or len(sk) not in (0, 2):
-        raise RuntimeError(f"expected res_branch of 5 modules and skip_con of 0 or 2, got {len(rb)} and {len(sk)}")
-    w1, s1, t1 = _fold_conv_bn(rb[0], rb[1], "res_branch[0]", 3)
-    w2, s2, t2 = _fold_conv_bn(rb[3], rb[4], "res_branch[3]", 3)
-    cin = w1.shape[1]
-    if w2.shape[1] != RES_C:
-        raise RuntimeError(f"res_branch[3]: expected {RES_C} input channels, got {w2.shape[1]}")
-    dev = torch.device(device)
-    skip = (None, None, None)
-    if len(sk) == 2:
-        ws, ss, ts = _fold_conv_bn(sk[0], sk[1], "skip_con[0]", 1)
-        if cin != 16 or ws.shape[1] != 16:
-            raise RuntimeError(f"a block with a 1x1x1 skip_con must take 16 channels, got {cin} and {ws.shape[1]}")
-        skip = (pack_pointwise_skip_weight(ws.reshape(RES_C, 16)).to(dev), ss.float().to(dev), ts.float().to(dev))
-    elif cin != RES_C:
-        raise RuntimeError(f"a block with an empty skip_con must take {RES_C} channels, got {cin}")
-    return Res3DParams(pack_conv3_weight(w1).to(dev), s1.float().to(dev), t1.float().to(dev),
-                       pack_conv3_weight(w2).to(dev), s2.float().to(dev), t2.float().to(dev), *skip)
-
-
-def _res_volume(what, x, name="x_cl", channels=(16, 32)):
-    """Checked contiguous (B, V, V, V, C) bf16 volume of the Res3DBlock kernel."""
-    if x.dtype != torch.bfloat16:
-        raise TypeError(f"{what}: {name} must be bfloat16, got {x.dtype}")
-    if x.dim() != 5 or x.shape[4] not in channels or len(set(x.shape[1:4])) != 1:
-        raise RuntimeError(f"{what}: {name} must be (B, V, V, V, {' | '.join(map(str, channels))}), got {tuple(x.shape)}")
-    V = x.shape[1]
-    if V % 16 != 0 or not 16 <= V <= 256:
-        raise RuntimeError(f"{what}: V must be a multiple of 16 in [16, 256], got {V}")
-    return x.contiguous()
-
-
-def _res_conv_params(what, packed, scale, shift, shape=(27, 2, 64, 8)):
-    if (tuple(packed.shape) != shape or packed.dtype != torch.bfloat16
-            or any(tuple(t.shape) != (RES_C,) or t.dtype != torch.float32 for t in (scale, shift))):
-        raise RuntimeError(f"{what}: packed weights, scale and shift must be what fold_res3d_block returns")
-    return packed.contiguous(), scale.contiguous(), shift.contiguous()
+    return _fold_res3d(_RES, block, device)
 
 
 def v2v_conv3(x_cl, packed, scale, shift, skip=None, skip_packed=None, skip_scale=None, skip_shift=None):
@@ -501,29 +723,7 @@ def v2v_conv3(x_cl, packed, scale, shift, skip=None, skip_packed=None, skip_scal
     with ``skip_packed``, ``skip_scale``, ``skip_shift`` goes through its folded 1x1x1 conv + BN.
     V is a multiple of 16 in [16, 256].  Non-finite voxels follow torch (mvn_hip.h).
     Inference-only."""
-    from . import _ops
-    what = "v2v_conv3"
-    _inference_only(what, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift,
-                    instead="the model's own Res3DBlock, which autograd records")
-    x = _res_volume(what, x_cl)
-    packed, scale, shift = _res_conv_params(what, packed, scale, shift)
-    pw = (skip_packed, skip_scale, skip_shift)
-    if skip is None:
-        if any(t is not None for t in pw):
-            raise RuntimeError(f"{what}: skip weights without a skip volume")
-        mode = SKIP_NONE
-    else:
-        mode = SKIP_POINTWISE if skip_packed is not None else SKIP_IDENTITY
-        skip = _res_volume(what, skip, "skip", (16,) if mode == SKIP_POINTWISE else (32,))
-        if tuple(skip.shape[:4]) != tuple(x.shape[:4]):
-            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)}")
-        if mode == SKIP_POINTWISE:
-            if skip_scale is None or skip_shift is None:
-                raise RuntimeError(f"{what}: a pointwise skip needs skip_packed, skip_scale and skip_shift")
-            pw = _res_conv_params(what, skip_packed, skip_scale, skip_shift, (2, 64, 8))
-        elif any(t is not None for t in pw):
-            raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
-    return _ops.call(_ops.v2v_conv3, x, packed, scale, shift, mode, skip, *pw)
+    return _conv3(_RES, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
 
 
 def res3d_block(x_cl, params, group_frames=0):
@@ -534,51 +734,32 @@ def res3d_block(x_cl, params, group_frames=0):
     it with the block's input as its skip.  Equal bit for bit to the two ``v2v_conv3`` launches on
     the whole batch.  Inference-only."""
     from . import _ops
-    what = "res3d_block"
+    what, lv = "res3d_block", _RES
     p = Res3DParams(*params)
     _inference_only(what, x_cl, *p, instead="the model's own Res3DBlock, which autograd records")
     pointwise = p.skip_packed is not None
-    x = _res_volume(what, x_cl, channels=(16,) if pointwise else (32,))
-    c1 = _res_conv_params(what, p.packed1, p.scale1, p.shift1)
-    c2 = _res_conv_params(what, p.packed2, p.scale2, p.shift2)
+    x = _volume(lv, what, x_cl, "x_cl", (16,) if pointwise else (32,))
+    c1 = _folded(what, p.packed1, p.scale1, p.shift1, lv.conv_shape[x.shape[4]], RES_C, lv.fold)
+    c2 = _folded(what, p.packed2, p.scale2, p.shift2, lv.conv_shape[RES_C], RES_C, lv.fold)
     if pointwise:
         if p.skip_scale is None or p.skip_shift is None:
             raise RuntimeError(f"{what}: a pointwise skip needs skip_packed, skip_scale and skip_shift")
-        sk = _res_conv_params(what, p.skip_packed, p.skip_scale, p.skip_shift, (2, 64, 8))
+        sk = _folded(what, p.skip_packed, p.skip_scale, p.skip_shift, lv.skip_shape, RES_C, lv.fold)
     else:
         sk = (None, None, None)
     return _ops.call(_ops.v2v_res3d, x, *c1, *c2, *sk, int(group_frames))
 
 
-class Res3DBlockCL(nn.Module):
+class Res3DBlockCL(_Res3DBlockCL):
     """Eval-mode replacement of a full-resolution Res3DBlock(16 | 32, 32) on a channels-last bf16
     volume: ``Res3DBlockCL.from_reference(block)(x_cl)``."""
-
-    def __init__(self, params):
-        super().__init__()
-        for name, t in zip(Res3DParams._fields, Res3DParams(*params)):
-            self.register_buffer(name, t)
-
-    @classmethod
-    def from_reference(cls, block, device="cuda"):
-        return cls(fold_res3d_block(block, device=device))
-
-    @property
-    def params(self):
-        return Res3DParams(*(getattr(self, name) for name in Res3DParams._fields))
+    _fold = staticmethod(fold_res3d_block)
 
     def forward(self, x_cl, group_frames=0):
         return res3d_block(x_cl, self.params, group_frames)
 
 
-# --------------------------------------------------------------------------- first pooled level
-# encoder_pool1, encoder_res1 (Res3DBlock(32, 64)), skip_res2 and decoder_res1 (Res3DBlock(64, 64))
-# and decoder_upsample1 with the last ``+ skip_x1`` (mvn/models/v2v.py:45-65, 105-135) on
-# channels-last bf16 volumes (csrc/v2v_interior.hip, DESIGN.md §4.13).
-WIDE_C = 64
-UP_CIN, UP_COUT = 64, 32
-
-
+# ---- 64 channels, first pooled level
 def max_pool2_cl(x_cl):
     """(B, V, V, V, C) bf16 channels-last -> (B, V/2, V/2, V/2, C): ``F.max_pool3d(x, 2, 2)`` bit
     for bit (mvn_v2v_maxpool2), NaN, infinities and signed zeros included.  V is even in [2, 256],
@@ -598,82 +779,12 @@ def max_pool2_cl(x_cl):
     return _ops.call(_ops.v2v_maxpool2, x_cl.contiguous())
 
 
-def pack_conv3_wide_weight(w):
-    """(64, cin, 3, 3, 3) float64, cin 32 | 64 -> (27, cin / 32, 4, 64, 8) bf16 as mvn_v2v_conv3_wide
-    reads it: [tap = (dx*3 + dy)*3 + dz][kp][m][lane][j]
-    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]."""
-    cin = w.shape[1]
-    wt = w.reshape(WIDE_C, cin, 27).permute(2, 0, 1)                                # [tap][cout][cin]
-    row, k = _mfma_a_rows()
-    packed = torch.stack([torch.stack([wt[:, (16 * m + row).view(64, 1).expand(64, 8), 32 * kp + k]
-                                       for m in range(4)], dim=1) for kp in range(cin // 32)], dim=1)
-    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
-
-
-def pack_pointwise_skip_wide_weight(w):
-    """(64, 32) float64 -> (4, 64, 8) bf16: [m][lane][j] = w[16 m + (lane & 15)][8 (lane >> 4) + j]."""
-    row, k = _mfma_a_rows()
-    packed = torch.stack([w[(16 * m + row).view(64, 1).expand(64, 8), k] for m in range(4)])
-    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
-
-
-def pack_upsample_weight(w):
-    """(64, 32, 2, 2, 2) float64 ConvTranspose3d weight -> (2, 16, 64, 8) bf16 as mvn_v2v_upsample2
-    reads it: [kp][m][lane][j] = w[32 kp + 8 (lane >> 4) + j][16 (m & 1) + (lane & 15)][dx][dy][dz]
-    with (dx*2 + dy)*2 + dz = m >> 1."""
-    wt = w.reshape(UP_CIN, UP_COUT, 8).permute(2, 1, 0)                             # [pos][cout][cin]
-    row, k = _mfma_a_rows()
-    packed = torch.stack([torch.stack([wt[m >> 1][(16 * (m & 1) + row).view(64, 1).expand(64, 8), 32 * kp + k]
-                                       for m in range(16)]) for kp in range(2)])
-    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
-
-
-def _fold_conv_bn_wide(conv, bn, what, ks, cins):
-    """(f64 weight, f64 scale, f64 shift) of an eval-mode Conv3d(cins -> 64, ks) + BatchNorm3d(64)."""
-    w = conv.weight.detach().to(torch.float64).cpu()
-    want = " | ".join(map(str, cins))
-    if w.dim() != 5 or w.shape[0] != WIDE_C or w.shape[1] not in cins or tuple(w.shape[2:]) != (ks,) * 3:
-        raise RuntimeError(f"{what}: expected a ({WIDE_C}, {want}, {ks}, {ks}, {ks}) Conv3d weight, got {tuple(w.shape)}")
-    pad = (ks - 1) // 2
-    if tuple(conv.stride) != (1, 1, 1) or tuple(conv.padding) != (pad,) * 3 or tuple(conv.dilation) != (1, 1, 1):
-        raise RuntimeError(f"{what}: expected stride 1, padding {pad} and no dilation")
-    if bn.running_mean is None or tuple(bn.running_mean.shape) != (WIDE_C,):
-        raise RuntimeError(f"{what}: expected a BatchNorm3d({WIDE_C}) with running statistics")
-    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
-    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(WIDE_C, dtype=torch.float64)
-    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
-    return w, s, shift
-
-
 def fold_res3d_block_wide(block, device="cuda"):
     """An eval-mode module with Res3DBlock's attributes and 32 | 64 -> 64 channels (``skip_con``
     [conv 1x1x1, BN] for 32, empty for 64) -> ``Res3DParams`` on ``device``: folded in float64
     exactly as ``fold_res3d_block``, packed as mvn_v2v_conv3_wide expects
     (``pack_conv3_wide_weight``, ``pack_pointwise_skip_wide_weight``)."""
-    rb, sk = block.res_branch, block.skip_con
-    if len(rb) != 5 or len(sk) not in (0, 2):
-        raise RuntimeError(f"expected res_branch of 5 modules and skip_con of 0 or 2, got {len(rb)} and {len(sk)}")
-    w1, s1, t1 = _fold_conv_bn_wide(rb[0], rb[1], "res_branch[0]", 3, (32, 64))
-    w2, s2, t2 = _fold_conv_bn_wide(rb[3], rb[4], "res_branch[3]", 3, (64,))
-    cin = w1.shape[1]
-    dev = torch.device(device)
-    skip = (None, None, None)
-    if len(sk) == 2:
-        ws, ss, ts = _fold_conv_bn_wide(sk[0], sk[1], "skip_con[0]", 1, (32,))
-        if cin != 32:
-            raise RuntimeError(f"a block with a 1x1x1 skip_con must take 32 channels, got {cin}")
-        skip = (pack_pointwise_skip_wide_weight(ws.reshape(WIDE_C, 32)).to(dev), ss.float().to(dev), ts.float().to(dev))
-    elif cin != WIDE_C:
-        raise RuntimeError(f"a block with an empty skip_con must take {WIDE_C} channels, got {cin}")
-    return Res3DParams(pack_conv3_wide_weight(w1).to(dev), s1.float().to(dev), t1.float().to(dev),
-                       pack_conv3_wide_weight(w2).to(dev), s2.float().to(dev), t2.float().to(dev), *skip)
-
-
-class UpsampleParams(NamedTuple):
-    """What ``fold_upsample_block`` returns: packed bf16 weights and f32 scale / shift."""
-    packed: torch.Tensor
-    scale: torch.Tensor
-    shift: torch.Tensor
+    return _fold_res3d(_WIDE, block, device)
 
 
 def fold_upsample_block(block, device="cuda"):
@@ -681,42 +792,7 @@ def fold_upsample_block(block, device="cuda"):
     32, 2, stride 2), BatchNorm3d(32), ReLU) -> ``UpsampleParams`` on ``device``: the ConvTranspose
     bias and the BN folded in float64, the weights rounded to bf16 and packed as
     mvn_v2v_upsample2 expects (``pack_upsample_weight``)."""
-    seq = getattr(block, "block", None)
-    if seq is None or len(seq) != 3 or not isinstance(seq[0], nn.ConvTranspose3d):
-        raise RuntimeError("expected block = [ConvTranspose3d, BatchNorm3d, ReLU]")
-    conv, bn = seq[0], seq[1]
-    w = conv.weight.detach().to(torch.float64).cpu()
-    if tuple(w.shape) != (UP_CIN, UP_COUT, 2, 2, 2):
-        raise RuntimeError(f"block[0]: expected a ({UP_CIN}, {UP_COUT}, 2, 2, 2) ConvTranspose3d weight, got {tuple(w.shape)}")
-    if (tuple(conv.stride) != (2, 2, 2) or tuple(conv.padding) != (0, 0, 0) or tuple(conv.output_padding) != (0, 0, 0)
-            or tuple(conv.dilation) != (1, 1, 1) or conv.groups != 1):
-        raise RuntimeError("block[0]: expected stride 2, no padding, no output padding, no dilation, one group")
-    if bn.running_mean is None or tuple(bn.running_mean.shape) != (UP_COUT,):
-        raise RuntimeError(f"block[1]: expected a BatchNorm3d({UP_COUT}) with running statistics")
-    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
-    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(UP_COUT, dtype=torch.float64)
-    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
-    dev = torch.device(device)
-    return UpsampleParams(pack_upsample_weight(w).to(dev), s.float().to(dev), shift.float().to(dev))
-
-
-def _wide_volume(what, x, name="x_cl", channels=(32, 64), vmax=128):
-    """Checked contiguous (B, V, V, V, C) bf16 volume of the first pooled level's kernels."""
-    if x.dtype != torch.bfloat16:
-        raise TypeError(f"{what}: {name} must be bfloat16, got {x.dtype}")
-    if x.dim() != 5 or x.shape[4] not in channels or len(set(x.shape[1:4])) != 1:
-        raise RuntimeError(f"{what}: {name} must be (B, V, V, V, {' | '.join(map(str, channels))}), got {tuple(x.shape)}")
-    V = x.shape[1]
-    if V % 16 != 0 or not 16 <= V <= vmax:
-        raise RuntimeError(f"{what}: {name}: V must be a multiple of 16 in [16, {vmax}], got {V}")
-    return x.contiguous()
-
-
-def _wide_params(what, packed, scale, shift, shape, channels=WIDE_C):
-    if (tuple(packed.shape) != shape or packed.dtype != torch.bfloat16
-            or any(tuple(t.shape) != (channels,) or t.dtype != torch.float32 for t in (scale, shift))):
-        raise RuntimeError(f"{what}: packed weights {shape}, scale and shift ({channels},) must be what the fold returns")
-    return packed.contiguous(), scale.contiguous(), shift.contiguous()
+    return _fold_upsample(_WIDE, block, device)
 
 
 def v2v_conv3_wide(x_cl, packed, scale, shift, skip=None, skip_packed=None, skip_scale=None, skip_shift=None):
@@ -726,29 +802,7 @@ def v2v_conv3_wide(x_cl, packed, scale, shift, skip=None, skip_packed=None, skip
     (B, V, V, V, 32) with ``skip_packed``, ``skip_scale``, ``skip_shift`` goes through its folded
     1x1x1 conv + BN.  V is a multiple of 16 in [16, 128].  Non-finite voxels follow torch
     (mvn_hip.h).  Inference-only."""
-    from . import _ops
-    what = "v2v_conv3_wide"
-    _inference_only(what, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift,
-                    instead="the model's own Res3DBlock, which autograd records")
-    x = _wide_volume(what, x_cl)
-    packed, scale, shift = _wide_params(what, packed, scale, shift, (27, x.shape[4] // 32, 4, 64, 8))
-    pw = (skip_packed, skip_scale, skip_shift)
-    if skip is None:
-        if any(t is not None for t in pw):
-            raise RuntimeError(f"{what}: skip weights without a skip volume")
-        mode = SKIP_NONE
-    else:
-        mode = SKIP_POINTWISE if skip_packed is not None else SKIP_IDENTITY
-        skip = _wide_volume(what, skip, "skip", (32,) if mode == SKIP_POINTWISE else (64,))
-        if tuple(skip.shape[:4]) != tuple(x.shape[:4]):
-            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)}")
-        if mode == SKIP_POINTWISE:
-            if skip_scale is None or skip_shift is None:
-                raise RuntimeError(f"{what}: a pointwise skip needs skip_packed, skip_scale and skip_shift")
-            pw = _wide_params(what, skip_packed, skip_scale, skip_shift, (4, 64, 8))
-        elif any(t is not None for t in pw):
-            raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
-    return _ops.call(_ops.v2v_conv3_wide, x, packed, scale, shift, mode, skip, *pw)
+    return _conv3(_WIDE, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
 
 
 def res3d_block_wide(x_cl, params):
@@ -756,35 +810,13 @@ def res3d_block_wide(x_cl, params):
     (B, V, V, V, 32 | 64) bf16 channels-last -> (B, V, V, V, 64) bf16, ``params`` from
     ``fold_res3d_block_wide``.  The hidden volume is a torch allocation (4.2 MB per frame at 32^3).
     Inference-only."""
-    what = "res3d_block_wide"
-    p = Res3DParams(*params)
-    _inference_only(what, x_cl, *p, instead="the model's own Res3DBlock, which autograd records")
-    pointwise = p.skip_packed is not None
-    x = _wide_volume(what, x_cl, channels=(32,) if pointwise else (64,))
-    h = v2v_conv3_wide(x, p.packed1, p.scale1, p.shift1)
-    if pointwise:
-        return v2v_conv3_wide(h, p.packed2, p.scale2, p.shift2, x, p.skip_packed, p.skip_scale, p.skip_shift)
-    if p.skip_scale is not None or p.skip_shift is not None:
-        raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
-    return v2v_conv3_wide(h, p.packed2, p.scale2, p.shift2, x)
+    return _res3d_two_launches(_WIDE, "res3d_block_wide", x_cl, params)
 
 
-class Res3DBlockWideCL(nn.Module):
+class Res3DBlockWideCL(_Res3DBlockCL):
     """Eval-mode replacement of a Res3DBlock(32 | 64, 64) on a channels-last bf16 volume:
     ``Res3DBlockWideCL.from_reference(block)(x_cl)``."""
-
-    def __init__(self, params):
-        super().__init__()
-        for name, t in zip(Res3DParams._fields, Res3DParams(*params)):
-            self.register_buffer(name, t)
-
-    @classmethod
-    def from_reference(cls, block, device="cuda"):
-        return cls(fold_res3d_block_wide(block, device=device))
-
-    @property
-    def params(self):
-        return Res3DParams(*(getattr(self, name) for name in Res3DParams._fields))
+    _fold = staticmethod(fold_res3d_block_wide)
 
     def forward(self, x_cl):
         return res3d_block_wide(x_cl, self.params)
@@ -796,125 +828,24 @@ def upsample2_add(x_cl, params, skip=None):
     bf16(relu(bn(conv_transpose(x))) + skip), the ReLU before the add, one rounding.  ``params``
     from ``fold_upsample_block``; ``skip`` (B, 2V, 2V, 2V, 32) bf16, or None for no add.  V is a
     multiple of 16 in [16, 128].  Inference-only."""
-    from . import _ops
-    what = "upsample2_add"
-    p = UpsampleParams(*params)
-    _inference_only(what, x_cl, *p, skip, instead="the model's own Upsample3DBlock, which autograd records")
-    x = _wide_volume(what, x_cl, channels=(UP_CIN,))
-    packed, scale, shift = _wide_params(what, p.packed, p.scale, p.shift, (2, 16, 64, 8), UP_COUT)
-    if skip is not None:
-        skip = _wide_volume(what, skip, "skip", (UP_COUT,), vmax=256)
-        B, V = x.shape[0], x.shape[1]
-        if tuple(skip.shape[:4]) != (B, 2 * V, 2 * V, 2 * V):
-            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)} upsampled")
-    return _ops.call(_ops.v2v_upsample2, x, packed, scale, shift, skip)
+    return _upsample2_add(_WIDE, "upsample2_add", x_cl, params, skip)
 
 
-class Upsample3DBlockCL(nn.Module):
+class Upsample3DBlockCL(_Upsample3DBlockCL):
     """Eval-mode replacement of Upsample3DBlock(64, 32) with the ``+ skip`` behind it."""
-
-    def __init__(self, params):
-        super().__init__()
-        for name, t in zip(UpsampleParams._fields, UpsampleParams(*params)):
-            self.register_buffer(name, t)
-
-    @classmethod
-    def from_reference(cls, block, device="cuda"):
-        return cls(fold_upsample_block(block, device=device))
-
-    @property
-    def params(self):
-        return UpsampleParams(self.packed, self.scale, self.shift)
+    _fold = staticmethod(fold_upsample_block)
 
     def forward(self, x_cl, skip=None):
         return upsample2_add(x_cl, self.params, skip)
 
 
-# --------------------------------------------------------------------------- 128-channel levels
-# encoder_pool2 ... decoder_upsample2 (mvn/models/v2v.py:108-132): the Res3DBlocks with 128 output
-# channels and the upsamples that take 128 channels, at any extent D in [1, 64], on channels-last
-# bf16 volumes (csrc/v2v_deep.hip, DESIGN.md §4.14).
-DEEP_C = 128
-DEEP_MAX_D = 64
-
-
-def pack_conv3_deep_weight(w):
-    """(128, cin, 3, 3, 3) float64, cin 64 | 128 -> (27, cin / 32, 8, 64, 8) bf16 as mvn_v2v_conv3_deep
-    reads it: [tap = (dx*3 + dy)*3 + dz][kp][m][lane][j]
-    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]."""
-    cin = w.shape[1]
-    wt = w.reshape(DEEP_C, cin, 27).permute(2, 0, 1)                                # [tap][cout][cin]
-    row, k = _mfma_a_rows()
-    packed = torch.stack([torch.stack([wt[:, (16 * m + row).view(64, 1).expand(64, 8), 32 * kp + k]
-                                       for m in range(8)], dim=1) for kp in range(cin // 32)], dim=1)
-    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
-
-
-def pack_pointwise_skip_deep_weight(w):
-    """(128, 64) float64 -> (2, 8, 64, 8) bf16: [kp][m][lane][j]
-    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j]."""
-    row, k = _mfma_a_rows()
-    packed = torch.stack([torch.stack([w[(16 * m + row).view(64, 1).expand(64, 8), 32 * kp + k] for m in range(8)])
-                          for kp in range(2)])
-    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
-
-
-def pack_upsample_deep_weight(w):
-    """(128, cout, 2, 2, 2) float64 ConvTranspose3d weight, cout 64 | 128 -> (4, 8 cout / 16, 64, 8)
-    bf16 as mvn_v2v_upsample2_deep reads it, with H = cout / 16 channel tiles per offset:
-    [kp][m][lane][j] = w[32 kp + 8 (lane >> 4) + j][16 (m % H) + (lane & 15)][dx][dy][dz]
-    with (dx*2 + dy)*2 + dz = m // H."""
-    cout = w.shape[1]
-    H = cout // 16
-    wt = w.reshape(DEEP_C, cout, 8).permute(2, 1, 0)                                # [pos][cout][cin]
-    row, k = _mfma_a_rows()
-    packed = torch.stack([torch.stack([wt[m // H][(16 * (m % H) + row).view(64, 1).expand(64, 8), 32 * kp + k]
-                                       for m in range(8 * H)]) for kp in range(4)])
-    return packed.to(torch.float32).to(torch.bfloat16).contiguous()
-
-
-def _fold_conv_bn_deep(conv, bn, what, ks, cins):
-    """(f64 weight, f64 scale, f64 shift) of an eval-mode Conv3d(cins -> 128, ks) + BatchNorm3d(128)."""
-    w = getattr(conv, "weight", None)
-    want = " | ".join(map(str, cins))
-    if not isinstance(conv, nn.Conv3d) or w.shape[0] != DEEP_C or w.shape[1] not in cins or tuple(w.shape[2:]) != (ks,) * 3:
-        got = tuple(w.shape) if w is not None else type(conv).__name__
-        raise RuntimeError(f"{what}: expected a ({DEEP_C}, {want}, {ks}, {ks}, {ks}) Conv3d weight, got {got}")
-    w = w.detach().to(torch.float64).cpu()
-    pad = (ks - 1) // 2
-    if tuple(conv.stride) != (1, 1, 1) or tuple(conv.padding) != (pad,) * 3 or tuple(conv.dilation) != (1, 1, 1):
-        raise RuntimeError(f"{what}: expected stride 1, padding {pad} and no dilation")
-    if bn.running_mean is None or tuple(bn.running_mean.shape) != (DEEP_C,):
-        raise RuntimeError(f"{what}: expected a BatchNorm3d({DEEP_C}) with running statistics")
-    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
-    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(DEEP_C, dtype=torch.float64)
-    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
-    return w, s, shift
-
-
+# ---- 128 channels, the levels below
 def fold_res3d_block_deep(block, device="cuda"):
     """An eval-mode module with Res3DBlock's attributes and 64 | 128 -> 128 channels (``skip_con``
     [conv 1x1x1, BN] for 64, empty for 128) -> ``Res3DParams`` on ``device``: folded in float64
     exactly as ``fold_res3d_block_wide``, packed as mvn_v2v_conv3_deep expects
     (``pack_conv3_deep_weight``, ``pack_pointwise_skip_deep_weight``)."""
-    rb, sk = getattr(block, "res_branch", None), getattr(block, "skip_con", None)
-    if rb is None or sk is None or len(rb) != 5 or len(sk) not in (0, 2):
-        raise RuntimeError("expected a module with Res3DBlock's res_branch of 5 modules and skip_con of 0 or 2, got "
-                           + type(block).__name__)
-    w1, s1, t1 = _fold_conv_bn_deep(rb[0], rb[1], "res_branch[0]", 3, (64, 128))
-    w2, s2, t2 = _fold_conv_bn_deep(rb[3], rb[4], "res_branch[3]", 3, (128,))
-    cin = w1.shape[1]
-    dev = torch.device(device)
-    skip = (None, None, None)
-    if len(sk) == 2:
-        ws, ss, ts = _fold_conv_bn_deep(sk[0], sk[1], "skip_con[0]", 1, (64,))
-        if cin != 64:
-            raise RuntimeError(f"a block with a 1x1x1 skip_con must take 64 channels, got {cin}")
-        skip = (pack_pointwise_skip_deep_weight(ws.reshape(DEEP_C, 64)).to(dev), ss.float().to(dev), ts.float().to(dev))
-    elif cin != DEEP_C:
-        raise RuntimeError(f"a block with an empty skip_con must take {DEEP_C} channels, got {cin}")
-    return Res3DParams(pack_conv3_deep_weight(w1).to(dev), s1.float().to(dev), t1.float().to(dev),
-                       pack_conv3_deep_weight(w2).to(dev), s2.float().to(dev), t2.float().to(dev), *skip)
+    return _fold_res3d(_DEEP, block, device)
 
 
 def fold_upsample_block_deep(block, device="cuda"):
@@ -922,35 +853,7 @@ def fold_upsample_block_deep(block, device="cuda"):
     64 | 128, 2, stride 2), BatchNorm3d, ReLU) -> ``UpsampleParams`` on ``device``: the ConvTranspose
     bias and the BN folded in float64, the weights rounded to bf16 and packed as
     mvn_v2v_upsample2_deep expects (``pack_upsample_deep_weight``)."""
-    seq = getattr(block, "block", None)
-    if seq is None or len(seq) != 3 or not isinstance(seq[0], nn.ConvTranspose3d):
-        raise RuntimeError("expected block = [ConvTranspose3d, BatchNorm3d, ReLU]")
-    conv, bn = seq[0], seq[1]
-    w = conv.weight.detach().to(torch.float64).cpu()
-    if w.dim() != 5 or w.shape[0] != DEEP_C or w.shape[1] not in (64, 128) or tuple(w.shape[2:]) != (2, 2, 2):
-        raise RuntimeError(f"block[0]: expected a ({DEEP_C}, 64 | 128, 2, 2, 2) ConvTranspose3d weight, got {tuple(w.shape)}")
-    cout = w.shape[1]
-    if (tuple(conv.stride) != (2, 2, 2) or tuple(conv.padding) != (0, 0, 0) or tuple(conv.output_padding) != (0, 0, 0)
-            or tuple(conv.dilation) != (1, 1, 1) or conv.groups != 1):
-        raise RuntimeError("block[0]: expected stride 2, no padding, no output padding, no dilation, one group")
-    if bn.running_mean is None or tuple(bn.running_mean.shape) != (cout,):
-        raise RuntimeError(f"block[1]: expected a BatchNorm3d({cout}) with running statistics")
-    s = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
-    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(cout, dtype=torch.float64)
-    shift = (b - bn.running_mean.detach().double().cpu()) * s + bn.bias.detach().double().cpu()
-    dev = torch.device(device)
-    return UpsampleParams(pack_upsample_deep_weight(w).to(dev), s.float().to(dev), shift.float().to(dev))
-
-
-def _deep_volume(what, x, name="x_cl", channels=(64, 128), dmax=DEEP_MAX_D):
-    """Checked contiguous (B, D, D, D, C) bf16 volume of the 128-channel levels' kernels."""
-    if x.dtype != torch.bfloat16:
-        raise TypeError(f"{what}: {name} must be bfloat16, got {x.dtype}")
-    if x.dim() != 5 or x.shape[4] not in channels or len(set(x.shape[1:4])) != 1:
-        raise RuntimeError(f"{what}: {name} must be (B, D, D, D, {' | '.join(map(str, channels))}), got {tuple(x.shape)}")
-    if not 1 <= x.shape[1] <= dmax:
-        raise RuntimeError(f"{what}: {name}: D must be in [1, {dmax}], got {x.shape[1]}")
-    return x.contiguous()
+    return _fold_upsample(_DEEP, block, device)
 
 
 def v2v_conv3_deep(x_cl, packed, scale, shift, skip=None, skip_packed=None, skip_scale=None, skip_shift=None):
@@ -960,29 +863,7 @@ def v2v_conv3_deep(x_cl, packed, scale, shift, skip=None, skip_packed=None, skip
     (B, D, D, D, 64) with ``skip_packed``, ``skip_scale``, ``skip_shift`` goes through its folded
     1x1x1 conv + BN.  D is any integer in [1, 64].  Non-finite voxels follow torch (mvn_hip.h);
     two calls on the same data return the same bits.  Inference-only."""
-    from . import _ops
-    what = "v2v_conv3_deep"
-    _inference_only(what, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift,
-                    instead="the model's own Res3DBlock, which autograd records")
-    x = _deep_volume(what, x_cl)
-    packed, scale, shift = _wide_params(what, packed, scale, shift, (27, x.shape[4] // 32, 8, 64, 8), DEEP_C)
-    pw = (skip_packed, skip_scale, skip_shift)
-    if skip is None:
-        if any(t is not None for t in pw):
-            raise RuntimeError(f"{what}: skip weights without a skip volume")
-        mode = SKIP_NONE
-    else:
-        mode = SKIP_POINTWISE if skip_packed is not None else SKIP_IDENTITY
-        skip = _deep_volume(what, skip, "skip", (64,) if mode == SKIP_POINTWISE else (128,))
-        if tuple(skip.shape[:4]) != tuple(x.shape[:4]):
-            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)}")
-        if mode == SKIP_POINTWISE:
-            if skip_scale is None or skip_shift is None:
-                raise RuntimeError(f"{what}: a pointwise skip needs skip_packed, skip_scale and skip_shift")
-            pw = _wide_params(what, skip_packed, skip_scale, skip_shift, (2, 8, 64, 8), DEEP_C)
-        elif any(t is not None for t in pw):
-            raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
-    return _ops.call(_ops.v2v_conv3_deep, x, packed, scale, shift, mode, skip, *pw)
+    return _conv3(_DEEP, x_cl, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
 
 
 def res3d_block_deep(x_cl, params):
@@ -990,35 +871,13 @@ def res3d_block_deep(x_cl, params):
     (B, D, D, D, 64 | 128) bf16 channels-last -> (B, D, D, D, 128) bf16, ``params`` from
     ``fold_res3d_block_deep``.  The hidden volume is a torch allocation (1 MB per frame at 16^3).
     Inference-only."""
-    what = "res3d_block_deep"
-    p = Res3DParams(*params)
-    _inference_only(what, x_cl, *p, instead="the model's own Res3DBlock, which autograd records")
-    pointwise = p.skip_packed is not None
-    x = _deep_volume(what, x_cl, channels=(64,) if pointwise else (128,))
-    h = v2v_conv3_deep(x, p.packed1, p.scale1, p.shift1)
-    if pointwise:
-        return v2v_conv3_deep(h, p.packed2, p.scale2, p.shift2, x, p.skip_packed, p.skip_scale, p.skip_shift)
-    if p.skip_scale is not None or p.skip_shift is not None:
-        raise RuntimeError(f"{what}: an identity skip takes no skip_scale / skip_shift")
-    return v2v_conv3_deep(h, p.packed2, p.scale2, p.shift2, x)
+    return _res3d_two_launches(_DEEP, "res3d_block_deep", x_cl, params)
 
 
-class Res3DBlockDeepCL(nn.Module):
+class Res3DBlockDeepCL(_Res3DBlockCL):
     """Eval-mode replacement of a Res3DBlock(64 | 128, 128) on a channels-last bf16 volume:
     ``Res3DBlockDeepCL.from_reference(block)(x_cl)``."""
-
-    def __init__(self, params):
-        super().__init__()
-        for name, t in zip(Res3DParams._fields, Res3DParams(*params)):
-            self.register_buffer(name, t)
-
-    @classmethod
-    def from_reference(cls, block, device="cuda"):
-        return cls(fold_res3d_block_deep(block, device=device))
-
-    @property
-    def params(self):
-        return Res3DParams(*(getattr(self, name) for name in Res3DParams._fields))
+    _fold = staticmethod(fold_res3d_block_deep)
 
     def forward(self, x_cl):
         return res3d_block_deep(x_cl, self.params)
@@ -1030,41 +889,17 @@ def upsample2_add_deep(x_cl, params, skip=None):
     (mvn_v2v_upsample2_deep): bf16(relu(bn(conv_transpose(x))) + skip), the ReLU before the add, one
     rounding.  ``params`` from ``fold_upsample_block_deep``; ``skip`` (B, 2D, 2D, 2D, cout) bf16, or
     None for no add.  D is any integer in [1, 64].  Inference-only."""
-    from . import _ops
-    what = "upsample2_add_deep"
-    p = UpsampleParams(*params)
-    _inference_only(what, x_cl, *p, skip, instead="the model's own Upsample3DBlock, which autograd records")
-    x = _deep_volume(what, x_cl, channels=(DEEP_C,))
-    cout = p.scale.shape[0] if p.scale.dim() == 1 else -1
-    if cout not in (64, 128):
-        raise RuntimeError(f"{what}: scale and shift must be (64 | 128,), got {tuple(p.scale.shape)}")
-    packed, scale, shift = _wide_params(what, p.packed, p.scale, p.shift, (4, 8 * cout // 16, 64, 8), cout)
-    if skip is not None:
-        skip = _deep_volume(what, skip, "skip", (cout,), dmax=2 * DEEP_MAX_D)
-        B, D = x.shape[0], x.shape[1]
-        if tuple(skip.shape[:4]) != (B, 2 * D, 2 * D, 2 * D):
-            raise RuntimeError(f"{what}: skip {tuple(skip.shape)} does not match x_cl {tuple(x.shape)} upsampled")
-    return _ops.call(_ops.v2v_upsample2_deep, x, packed, scale, shift, skip)
+    return _upsample2_add(_DEEP, "upsample2_add_deep", x_cl, params, skip)
 
 
-class Upsample3DBlockDeepCL(nn.Module):
+class Upsample3DBlockDeepCL(_Upsample3DBlockCL):
     """Eval-mode replacement of Upsample3DBlock(128, 64 | 128) with the ``+ skip`` behind it."""
-
-    def __init__(self, params):
-        super().__init__()
-        for name, t in zip(UpsampleParams._fields, UpsampleParams(*params)):
-            self.register_buffer(name, t)
-
-    @classmethod
-    def from_reference(cls, block, device="cuda"):
-        return cls(fold_upsample_block_deep(block, device=device))
-
-    @property
-    def params(self):
-        return UpsampleParams(self.packed, self.scale, self.shift)
+    _fold = staticmethod(fold_upsample_block_deep)
 
     def forward(self, x_cl, skip=None):
         return upsample2_add_deep(x_cl, self.params, skip)
+
+
 
 
 # the folded modules of ``V2VEval.deep`` in the order ``v2v_interior_deep_cl`` takes them
