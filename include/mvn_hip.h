@@ -41,6 +41,8 @@
  *   mvn_algebraic_triangulate <- mvn/models/triangulation.py:164-191 (AlgebraicTriangulationNet's
  *                           forward after the backbone: mvn_softargmax2d, the confidence
  *                           normalisation, the upscale and mvn_dlt in one launch)
+ *   mvn_feature_conv       <- mvn/models/triangulation.py:238-240, :345 process_features,
+ *                           Conv2d(256, 32, 1)
  *
  * Conventions
  *   - Every buffer is caller-owned device memory (hipMalloc / torch), contiguous,
@@ -505,6 +507,37 @@ int mvn_v2v_conv3_deep(const void* x, int cin, const void* weight_packed, const 
 size_t mvn_v2v_upsample2_deep_packed_weight_bytes(int cout);
 int mvn_v2v_upsample2_deep(const void* x, int cout, const void* weight_packed, const float* scale,
                            const float* shift, const void* skip, void* out, int B, int D, void* stream);
+
+/*
+ * process_features of the volumetric model (triangulation.py:238-240, :345): Conv2d(cin, 32, 1) over
+ * NCHW maps, on the f32-input MFMA (v_mfma_f32_32x32x2_f32).  No pack step:
+ *   x       (n_images, cin, H, W)  x_dtype (f32 | bf16), contiguous
+ *   weight  (32, cin)              f32 row-major, the convolution's own weight
+ *   bias    (32)                   f32, or NULL for zeros
+ *   out     (n_images, 32, H, W)   out_dtype (f32 | bf16), contiguous; all four dtype pairs
+ * One arithmetic, defined bit for bit, for every dtype pair and both load paths:
+ *   acc = bias[co];  for ci = 0 .. cin-1 in ascending order:  acc = fmaf(weight[co][ci], x[n][ci][p], acc)
+ * An f32 out is acc, a bf16 out acc rounded to nearest-even; a bf16 x is widened to f32 (exact).
+ * Non-finite values follow the chain: a NaN or infinite x[n][ci][p] reaches the 32 outputs of pixel
+ * p of image n and no other.
+ *   cout      must be 32
+ *   cin       a multiple of 32 in [32, 512]
+ *   H, W      any values >= 1; n_images * H * W == 0 returns MVN_OK without a launch
+ *   4 GB      one image's maps, cin * H * W * sizeof(x element), must not exceed 2^31 - 1 bytes
+ *             (in-image byte offsets are 32-bit, and every load goes through a range-checked buffer
+ *             resource of one image); the whole batch may: the image base is 64-bit
+ * Alignment: x and out need only the alignment of their element type, at any H * W.  The kernel
+ * chooses per call from the actual pointers and H * W: where H * W % 4 == 0, x is aligned to four
+ * of its elements (16 bytes f32, 8 bytes bf16) and out to four of its, it loads 16 (8) bytes and
+ * stores 16 (8) bytes per lane; everywhere else it loads and stores single elements.  Both paths
+ * return the same bits.  No load touches a byte outside x's n_images * cin * H * W elements and no
+ * store a byte outside out's.
+ * Checked before any HIP call: MVN_ERR_ARG for a NULL x, weight or out or an unknown dtype code;
+ * MVN_ERR_SHAPE for another cout or cin, a negative extent, an image above the 2^31 - 1 bytes, or
+ * n_images * ceil(H * W / 128) above INT_MAX / 2.  Stream-ordered, allocates nothing, reentrant.
+ */
+int mvn_feature_conv(const void* x, int x_dtype, const float* weight, const float* bias, void* out,
+                     int out_dtype, int64_t n_images, int cin, int cout, int H, int W, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

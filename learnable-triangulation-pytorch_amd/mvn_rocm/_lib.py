@@ -86,6 +86,8 @@ SIGNATURES = {
                            + [_c_void_p] * 4 + [_c_int, _c_int, _c_void_p]),
     "mvn_v2v_upsample2_deep_packed_weight_bytes": (_c_size_t, [_c_int]),
     "mvn_v2v_upsample2_deep": (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 5 + [_c_int, _c_int, _c_void_p]),
+    "mvn_feature_conv": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_i64]
+                         + [_c_int] * 4 + [_c_void_p]),
     "mvn_unproject_backward": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
                                         _c_void_p, _c_void_p] + [_c_int] * 8 + [_c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward_workspace_bytes": (_c_size_t, [_c_int] * 5),

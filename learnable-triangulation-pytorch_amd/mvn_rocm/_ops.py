@@ -403,6 +403,32 @@ def _(x, packed, scale, shift, skip):
     return x.new_empty((B, 2 * D, 2 * D, 2 * D, scale.shape[0]), dtype=torch.bfloat16)
 
 
+# --------------------------------------------------------------------------- feature conv (process_features)
+FEATURE_COUT = 32             # csrc/feature_conv.hip: the 32 rows of one 32x32x2 f32 MFMA
+
+
+@_op("feature_conv")
+def feature_conv(x: Tensor, weight: Tensor, bias: Optional[Tensor], out_dtype: int) -> Tensor:
+    """x (M,Cin,H,W) f32|bf16 contiguous, weight (32,Cin) f32, bias (32,) f32 or None (zeros) ->
+    (M,32,H,W) of dtype code `out_dtype`: Conv2d(Cin, 32, 1) as an ascending fmaf chain
+    (csrc/feature_conv.hip)."""
+    _require_gpu(x, weight, bias)
+    M, cin, H, W = x.shape
+    out = torch.empty((M, FEATURE_COUT, H, W), dtype=_CODE_DTYPE[out_dtype], device=x.device)
+    if out.numel() == 0:                  # no image or no pixel: nothing to launch
+        return out
+    code = _lib.load().mvn_feature_conv(x.data_ptr(), _DTYPE_CODE[x.dtype], weight.data_ptr(), _ptr(bias),
+                                        out.data_ptr(), out_dtype, M, cin, weight.shape[0], H, W, _stream(x))
+    _lib.check(code, "mvn_feature_conv")
+    return out
+
+
+@feature_conv.register_fake
+def _(x, weight, bias, out_dtype):
+    M, cin, H, W = x.shape
+    return x.new_empty((M, FEATURE_COUT, H, W), dtype=_CODE_DTYPE[out_dtype])
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,
