@@ -24,6 +24,10 @@
 //     epilogue's per-channel constants and pointwise-skip fragments wait in LDS, which keeps
 //     every instantiation out of scratch (budget: DESIGN.md §4.13).
 //
+// The tile, the ring's chunk positions and the staging descriptor are v2v_halo.hpp's, shared with
+// v2v_conv3; this kernel gives the descriptor an 11-bit LDS index (a slice of 128-byte voxels is
+// 1440 chunks), which leaves 17 bits of offset (V <= 128).
+//
 // Upsample.  Per input voxel a 64 -> 8 * 32 matrix product: A = 16 rows (position, channel) x
 // 32 K-slots held in registers (32 fragments, 128 VGPRs, loaded once per wave), B = the 64
 // channels of 16 z-consecutive voxels read straight from global memory (no halo), D = 16 tiles
@@ -33,25 +37,12 @@
 // Pool.  One thread per output voxel and 8 channels: eight 16-byte loads, one 16-byte store.
 #include <climits>
 
-#include "mfma.hpp"
+#include "v2v_halo.hpp"
 
 namespace mvn {
 namespace {
 
-constexpr int CO = 64, NTAP = 27, MT = CO / 16;
-constexpr int TX = 4, TY = 8, TZ = 16;
-constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2;                 // 6, 10, 18
-constexpr int kWaves = 4, kThreads = kWaves * kWave;
-constexpr int kRows = TY / kWaves;                                   // output y-rows per wave: 2
-
-// LDS position of 16-byte channel chunk c of a halo voxel at halo z index hz.  Four chunks
-// (64-byte voxels): v2v_res3d's swizzle.  Eight chunks (128-byte voxels): voxel pairs rotate
-// through the 8 positions, so the 16 z-consecutive voxels of one B read (same chunk, any start)
-// fall on 16 distinct 16-byte slots of the 256-byte bank row.
-template <int CH>
-__device__ __forceinline__ int chunk_pos(int c, int hz) {
-  return CH == 4 ? (c ^ (((hz >> 2) & 1) << 1)) : (c ^ ((hz >> 1) & 7));
-}
+constexpr int CO = 64, MT = CO / 16;
 
 template <int CIN, int MODE>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void v2v_conv3_wide(
@@ -59,15 +50,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     const float* __restrict__ shift, const uint16_t* __restrict__ skip, const uint4* __restrict__ wskip,
     const float* __restrict__ scale_s, const float* __restrict__ shift_s, uint16_t* __restrict__ out, int V,
     int segTiles) {
-  constexpr int CH = CIN / 8;                                // 16-byte chunks per voxel record: 4 | 8
+  using R = Ring<CIN, 11>;                                   // 11-bit LDS index, 17-bit offset: V <= 128
+  constexpr int CH = R::CH, kHaloChunks = R::kHaloChunks, kStage = R::kStage;   // kStage: 12 | 23
   constexpr int KP = CIN / 32;                               // K-passes per tap
   constexpr int NS = 3 * KP * 2;                             // steps per tile: (dz, K-pass, channel half)
   constexpr int kWChunks = NTAP * KP * MT * kWave;           // 16-byte chunks of the packed weights
-  constexpr int kSliceChunks = HY * HZ * CH;                 // 720 | 1440 chunks per x-slice
-  constexpr int kSlotBytes = kSliceChunks * 16;              // 11,520 | 23,040 B
-  constexpr int kHaloChunks = HX * kSliceChunks;
-  constexpr int kStage = (TX * kSliceChunks + kThreads - 1) / kThreads;   // new-slice chunks per thread: 12 | 23
-  static_assert(kSliceChunks <= 2048, "the staging descriptor holds an 11-bit LDS index");
   __shared__ uint4 halo[kHaloChunks];                        // ring of HX x-slices: [slot][hy][hz][chunk]
   __shared__ __attribute__((aligned(16))) float tab[4][CO];  // scale, shift, skip scale, skip shift
   __shared__ uint4 wsl[MT * kWave];                          // POINTWISE: the skip's A fragments [m][lane]
@@ -85,22 +72,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
   // one frame per resource: a tap outside the volume reads zero, never the neighbouring frame
   const __amdgpu_buffer_rsrc_t irs = make_rsrc(in + size_t(b) * nvox * CIN, uint32_t(nvox * CIN * 2));
 
-  // halo chunk q of the slices gx0, gx0 + 1, ...: its global byte offset (kOob: zero) and its
-  // LDS index in the ring (slice gx sits in slot (gx + 1) mod HX)
-  auto chunk_src = [&](int gx0, int q, int total) -> uint32_t {
-    const int sl = q / kSliceChunks, rem = q - sl * kSliceChunks;
-    const int v = rem / CH, c = rem % CH;
-    const int hz = v % HZ, hy = v / HZ;
-    const int gx = gx0 + sl, gy = y0 + hy - 1, gz = z0 + hz - 1;
-    const bool ok = (q < total) & (unsigned(gx) < unsigned(V)) & (unsigned(gy) < unsigned(V)) &
-                    (unsigned(gz) < unsigned(V));
-    return ok ? uint32_t(((size_t(gx) * V + gy) * V + gz) * CIN * 2 + c * 16) : kOob;
-  };
-  auto chunk_dst = [&](int gx0, int q) -> int {
-    const int sl = q / kSliceChunks, rem = q - sl * kSliceChunks;
-    const int v = rem / CH, c = rem % CH;
-    return ((gx0 + sl + 1 + HX) % HX) * kSliceChunks + v * CH + chunk_pos<CH>(c, v % HZ);
-  };
   auto ld_chunk = [&](uint32_t off) {
     return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(irs, off, 0, 0));
   };
@@ -110,42 +81,21 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     for (int i0 = 0; i0 * kThreads < kHaloChunks; i0 += kBatch) {
       uint4 vals[kBatch];
 #pragma unroll
-      for (int u = 0; u < kBatch; ++u) vals[u] = ld_chunk(chunk_src(gx0, t + (i0 + u) * kThreads, kHaloChunks));
+      for (int u = 0; u < kBatch; ++u) vals[u] = ld_chunk(R::chunk_src(gx0, t + (i0 + u) * kThreads, kHaloChunks, y0, z0, V));
 #pragma unroll
       for (int u = 0; u < kBatch; ++u) {
         const int q = t + (i0 + u) * kThreads;
-        MVN_DASSERT(q >= kHaloChunks || (chunk_dst(gx0, q) >= 0 && chunk_dst(gx0, q) < kHaloChunks));
-        if (q < kHaloChunks) halo[chunk_dst(gx0, q)] = vals[u];
+        MVN_DASSERT(q >= kHaloChunks || (R::chunk_dst(gx0, q) >= 0 && R::chunk_dst(gx0, q) < kHaloChunks));
+        if (q < kHaloChunks) halo[R::chunk_dst(gx0, q)] = vals[u];
       }
     }
   }
 
   // Per-tile staging of chunk q = t + u * kThreads (u < kStage) of the 4 new slices: the
-  // in-slice part is tile-invariant and decoded once into a packed descriptor:
-  // bit 0 valid (q in range), bits 1-2 slice, bits 3-13 LDS index within the slot,
-  // bit 14 y/z inside the volume, bits 15-31 (gy * V + gz) * CH + c (V <= 128, CH <= 8: 17 bits).
+  // in-slice part is tile-invariant and decoded once into a packed descriptor
   uint32_t sdesc[kStage];
 #pragma unroll
-  for (int u = 0; u < kStage; ++u) {
-    const int q = t + u * kThreads;
-    const int sl = q / kSliceChunks, rem = q - sl * kSliceChunks;
-    const int v = rem / CH, c = rem % CH;
-    const int hz = v % HZ, hy = v / HZ;
-    const int gy = y0 + hy - 1, gz = z0 + hz - 1;
-    const bool valid = q < TX * kSliceChunks;
-    const bool yz = (unsigned(gy) < unsigned(V)) & (unsigned(gz) < unsigned(V));
-    const int li = v * CH + chunk_pos<CH>(c, hz);
-    MVN_DASSERT(!valid || (sl >= 0 && sl < TX && li >= 0 && li < kSliceChunks));
-    MVN_DASSERT(!yz || uint32_t((gy * V + gz) * CH + c) < (1u << 17));
-    sdesc[u] = (valid ? 1u : 0u) | (uint32_t(sl & 3) << 1) | (uint32_t(li) << 3) |
-               (yz ? (1u << 14) | (uint32_t((gy * V + gz) * CH + c) << 15) : 0u);
-  }
-  auto stage_src = [&](int u, int gx0) -> uint32_t {
-    const uint32_t d = sdesc[u];
-    const int gx = gx0 + int((d >> 1) & 3u);
-    const bool ok = ((d & ((1u << 14) | 1u)) == ((1u << 14) | 1u)) & (unsigned(gx) < unsigned(V));
-    return ok ? uint32_t(gx) * uint32_t(V * V * CIN * 2) + (d >> 15) * 16u : kOob;
-  };
+  for (int u = 0; u < kStage; ++u) sdesc[u] = R::describe1(t + u * kThreads, y0, z0, V);
 
   const int c = lane & 15, g = lane >> 4;
   // byte offset, within a slot, of the lane's B chunk of halo row 2 w at z offset dz, K-pass kp
@@ -200,18 +150,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     // in flight under the MFMAs: the next tile's 4 new slices
     uint4 sv[kStage];
 #pragma unroll
-    for (int u = 0; u < kStage; ++u) sv[u] = ld_chunk(more ? stage_src(u, gxn) : kOob);
+    for (int u = 0; u < kStage; ++u) sv[u] = ld_chunk(more ? R::stage_src(sdesc[u], gxn, V) : kOob);
     // voxel (x0 + x, y0 + 2 w + yl, z0 + c) of the frame
     auto vox = [&](int x, int yl) { return ((size_t(b) * V + (x0 + x)) * V + (y0 + w * kRows + yl)) * V + z0 + c; };
 
     uint32_t sb[HX];                          // slot of halo x index hx (gx = x0 - 1 + hx), bytes
     const int s0 = x0 % HX;
 #pragma unroll
-    for (int hx = 0; hx < HX; ++hx) {
-      const int slot = s0 + hx >= HX ? s0 + hx - HX : s0 + hx;
-      MVN_DASSERT(slot >= 0 && slot < HX);
-      sb[hx] = uint32_t(slot * kSlotBytes);
-    }
+    for (int hx = 0; hx < HX; ++hx) sb[hx] = R::slot_bytes(s0, hx);
     f32x4_t acc[TX][kRows][MT];
 #pragma unroll
     for (int x = 0; x < TX; ++x)
@@ -256,13 +202,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
       for (int u = 0; u < kStage; ++u) {
         const uint32_t d = sdesc[u];
-        if (d & 1u) {
-          int slot = ((gxn + 1) % HX) + int((d >> 1) & 3u);
-          if (slot >= HX) slot -= HX;
-          const int li = slot * kSliceChunks + int((d >> 3) & 2047u);
-          MVN_DASSERT(li >= 0 && li < kHaloChunks);
-          halo[li] = sv[u];
-        }
+        if (d & 1u) halo[R::stage_dst(d, (gxn + 1) % HX)] = sv[u];
       }
     }
 

@@ -10,7 +10,7 @@ import pytest
 import torch
 from torch import nn
 
-from test_gpu_v2v_res3d import V2VModel, randomise
+from v2v_kit import V2VModel, randomise
 
 OK, ARG, SHAPE = 0, -1, -2
 F32, BF16 = 0, 1

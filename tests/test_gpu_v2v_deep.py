@@ -2,8 +2,8 @@
 128 output channels and the 128-channel upsample at any extent D in [1, 64], the block, and
 V2VEval(half_res="kernels", deep="kernels") (MI355X only).
 
-The method is tests/test_gpu_v2v_interior.py's: operands for which the kernel's f32 arithmetic is
-exact in any summation order (integers in [-4, 4]: sums stay below 27 * 128 * 16 < 2^24; scales
+The method is tests/v2v_kit.py's, on its 128-channel record: operands for which the kernel's f32
+arithmetic is exact in any summation order (integers in [-4, 4]: sums stay below 27 * 128 * 16 < 2^24; scales
 +-2^k, shifts multiples of 1/4), compared bit for bit against torch on the CPU.
 
 The kernels flatten the voxels of all frames into groups of 16, so the shapes are the small ones
@@ -13,102 +13,26 @@ voxels.  The conv picks its wave tile (voxel groups x channel tiles = 1 x 2, 2 x
 the number of groups: all of the above run 1 x 2, so (1, 26) and (1, 33) (1099 and 2247 groups, both
 ragged in the group and in the tile) run the other two.  Reads nothing outside the repository.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from conftest import assert_parity_with_nans
-from test_gpu_v2v_interior import MODE_NAME, chain_kernels, exact_scale_shift
-from test_gpu_v2v_res3d import (E2E_MULT, E2E_SIDE, IDENTITY, NONE, POINTWISE, Res3DBlock, assert_same_bits, banded,
-                                bands_intact, BAND, bf16_full, bf16_operand_model, bf16r, bits, cl, e2e_case,
-                                lattice_reference, ncdhw, per_channel, randomise, stand_in_model)
+from v2v_kit import (BAND, DEEP, E2E_MULT, E2E_SIDE, IDENTITY, MODE_NAME, NONE, POINTWISE, UP_DEEP, Res3DBlock,
+                     Upsample3DBlock, assert_same_bits, banded, bands_intact, bf16_full, bf16_operand_model, bf16r, bits,
+                     box_mask, chain_deep, chain_kernels, check_bound, cl, e2e_case, lattice_input, lattice_reference,
+                     ncdhw, per_channel, randomise, stand_in_model)
 
 CO = 128
 SKIP_C = {NONE: 0, IDENTITY: 128, POINTWISE: 64}
+# the method of tests/v2v_kit.py on the 128-channel level and its upsample
+DeepCase, pack_deep, exact_scale_shift = DEEP.case, DEEP.pack, DEEP.exact_scale_shift
+integer_case, parity_case, random_case = DEEP.integer_case, DEEP.parity_case, DEEP.random_case
+UpCase, up_integer_case = UP_DEEP.case, UP_DEEP.integer_case
 SHAPES = ((1, 1), (3, 1), (2, 2), (3, 3), (1, 4), (3, 5), (2, 8), (1, 16))
 DEEP_KINDS = ((64, NONE), (64, POINTWISE), (128, NONE), (128, IDENTITY), (128, POINTWISE))
 DEEP_IDS = [f"{c}_{MODE_NAME[m]}" for c, m in DEEP_KINDS]
-
-
-# ----------------------------------------------------------------------------- conv: helpers
-def pack_deep(w, device):
-    from mvn_rocm import v2v
-    assert bool((w.bfloat16().float() == w).all())
-    return v2v.pack_conv3_deep_weight(w.double()).to(device)
-
-
-class DeepCase:
-    """Operands of one mvn_v2v_conv3_deep launch on the CPU (f32 tensors holding bf16-exact values)."""
-
-    def __init__(self, x, w, scale, shift, mode=NONE, skip=None, ws=None, scale_s=None, shift_s=None):
-        self.x, self.w, self.scale, self.shift, self.mode = x, w, scale, shift, mode
-        self.skip, self.ws, self.scale_s, self.shift_s = skip, ws, scale_s, shift_s
-
-    def args(self, device, x_dev=None, skip_dev=None):
-        from mvn_rocm import v2v
-        a = [cl(self.x, device) if x_dev is None else x_dev, pack_deep(self.w, device), self.scale.to(device),
-             self.shift.to(device)]
-        if self.mode != NONE:
-            a.append(cl(self.skip, device) if skip_dev is None else skip_dev)
-        if self.mode == POINTWISE:
-            a += [v2v.pack_pointwise_skip_deep_weight(self.ws.double()).to(device), self.scale_s.to(device),
-                  self.shift_s.to(device)]
-        return a
-
-    def run(self, device, x_dev=None, skip_dev=None):
-        from mvn_rocm import v2v
-        return v2v.v2v_conv3_deep(*self.args(device, x_dev, skip_dev))
-
-    def abs_sum(self):
-        """The largest sum of |x w| over an output, non-finite voxels left out."""
-        finite = torch.where(torch.isfinite(self.x), self.x, torch.zeros_like(self.x))
-        return float(F.conv3d(finite.abs(), self.w.abs(), None, padding=1).max())
-
-    def pre_relu(self, exact=True):
-        """r of the contract in float64; the convs in f32 on the CPU when ``exact`` (guarded: the sum
-        of |x w| is below 2^24, so no order of accumulation rounds), else in float64."""
-        x, w = self.x, self.w
-        if exact:
-            assert self.abs_sum() < 2.0 ** 24
-            acc = F.conv3d(x, w, None, padding=1).double()
-        else:
-            acc = F.conv3d(x.double(), w.double(), None, padding=1)
-        r = acc * per_channel(self.scale) + per_channel(self.shift)
-        if self.mode == IDENTITY:
-            r = r + self.skip.double()
-        elif self.mode == POINTWISE:
-            w1 = self.ws.view(CO, 64, 1, 1, 1)
-            acc_s = F.conv3d(self.skip, w1).double() if exact else F.conv3d(self.skip.double(), w1.double())
-            r = r + (acc_s * per_channel(self.scale_s) + per_channel(self.shift_s))
-        return r
-
-    def reference(self):
-        r = self.pre_relu()
-        assert not bool((torch.signbit(r) & (r == 0)).any()), "the pre-relu reference holds a -0"
-        return torch.where(r <= 0, torch.zeros_like(r), r).float().bfloat16(), r
-
-
-def integer_case(B, D, cin, mode, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(-4, 5, (B, cin, D, D, D), generator=g).float()
-    w = torch.randint(-4, 5, (CO, cin, 3, 3, 3), generator=g).float()
-    case = DeepCase(x, w, *exact_scale_shift(seed + 1, CO), mode)
-    if mode != NONE:
-        case.skip = torch.randint(-4, 5, (B, SKIP_C[mode], D, D, D), generator=g).float()
-    if mode == POINTWISE:
-        case.ws = torch.randint(-4, 5, (CO, 64), generator=g).float()
-        case.scale_s, case.shift_s = exact_scale_shift(seed + 2, CO)
-    return case
-
-
-@functools.lru_cache(maxsize=None)
-def parity_case(B, D, cin, mode):
-    case = integer_case(B, D, cin, mode, seed=1000 * B + D + 7 * cin + mode)
-    ref, r = case.reference()
-    return case, ref, r
 
 
 # ----------------------------------------------------------------------------- conv: exact parity
@@ -146,18 +70,6 @@ def test_deep_exact_parity_larger_wave_tiles(device, B, D, cin, mode):
 
 # ----------------------------------------------------------------------------- conv: impulses
 LATTICE_B, LATTICE_D, LATTICE_OFFS = 2, 16, (0, 2)
-
-
-def lattice_input(cin, off, g):
-    """Impulses at the voxels off, off + 3, ... of every axis, one channel each."""
-    B, D = LATTICE_B, LATTICE_D
-    x = torch.zeros((B, cin, D, D, D))
-    n = torch.arange(off, D, 3).numel()
-    ch = (torch.arange(B * n ** 3).view(B, n, n, n) * 5 + 11 * torch.arange(B).view(B, 1, 1, 1)) % cin
-    sub = torch.zeros(B, cin, n, n, n).scatter_(1, ch.unsqueeze(1), bf16_full((B, 1, n, n, n), g))
-    x[:, :, off::3, off::3, off::3] = sub
-    assert int((x != 0).sum()) == B * n ** 3
-    return x
 
 
 def skip_lattice(g):
@@ -318,13 +230,6 @@ def special_voxels(D):
     return ((0, 0, 0), (D - 1, D // 2, D - 1), (D // 2, D // 2, D // 2))
 
 
-def box_mask(D, voxels, pad):
-    m = np.zeros((D, D, D), bool)
-    for px, py, pz in voxels:
-        m[max(px - pad, 0):px + pad + 1, max(py - pad, 0):py + pad + 1, max(pz - pad, 0):pz + pad + 1] = True
-    return m
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin", (64, 128))
 @pytest.mark.parametrize("D", (3, 5))
@@ -416,44 +321,6 @@ def test_deep_no_reads_or_writes_outside_the_tensors(device, B, D, cin, mode):
 
 
 # ----------------------------------------------------------------------------- conv: random data
-def random_case(B, D, cin, mode, seed, x=None):
-    g = torch.Generator().manual_seed(seed)
-    if x is None:
-        x = bf16r(torch.randn(B, cin, D, D, D, generator=g))
-    w = bf16r(torch.randn(CO, cin, 3, 3, 3, generator=g) * (2.0 / (27 * (cin + CO))) ** 0.5 * 3)
-    scale = (0.75 + 0.5 * torch.rand(CO, generator=g)) * torch.where(torch.arange(CO) % 5 == 2, -1.0, 1.0)
-    case = DeepCase(x, w, scale, 0.2 * torch.randn(CO, generator=g), mode)
-    if mode != NONE:
-        case.skip = bf16r(torch.randn(B, SKIP_C[mode], D, D, D, generator=g))
-    if mode == POINTWISE:
-        case.ws = bf16r(torch.randn(CO, 64, generator=g) * 0.2)
-        case.scale_s = 0.75 + 0.5 * torch.rand(CO, generator=g)
-        case.shift_s = 0.2 * torch.randn(CO, generator=g)
-    return case
-
-
-def check_bound(case, got, what):
-    """|got - ref| <= 2^-8 |ref| + gamma S per element, gamma = (27 Cin + Cin_skip + 4) 2^-24 (half a
-    bf16 ulp plus the worst-case f32 summation bound of the contract), ref the
-    float64 restatement, S the sum of the absolute products; returns the worst fraction of the bar."""
-    cin = case.x.shape[1]
-    gamma = (27 * cin + SKIP_C[case.mode] + 4) * 2.0 ** -24
-    r = case.pre_relu(exact=False)
-    ref = torch.where(r <= 0, torch.zeros_like(r), r)
-    S = F.conv3d(case.x.double().abs(), case.w.double().abs(), None, padding=1) * per_channel(case.scale).abs() \
-        + per_channel(case.shift).abs()
-    if case.mode == IDENTITY:
-        S = S + case.skip.double().abs()
-    elif case.mode == POINTWISE:
-        S = S + F.conv3d(case.skip.double().abs(), case.ws.double().abs().view(CO, 64, 1, 1, 1)) \
-            * per_channel(case.scale_s).abs() + per_channel(case.shift_s).abs()
-    bar = 2.0 ** -8 * ref.abs() + gamma * S
-    frac = float(((got.double() - ref).abs() / bar).max())
-    print(f"{what}: worst |got - ref| / bar = {frac:.4f}")
-    assert frac <= 1.0
-    return frac
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin,mode", ((64, POINTWISE), (128, IDENTITY)), ids=("64to128_pointwise", "128to128_identity"))
 @pytest.mark.parametrize("D", (5, 16))
@@ -474,57 +341,6 @@ def test_deep_random_data_against_float64_restatement(device, D, cin, mode):
 
 
 # ----------------------------------------------------------------------------- upsample
-class UpCase:
-    """Operands of one mvn_v2v_upsample2_deep launch on the CPU (f32 tensors of bf16-exact values)."""
-
-    def __init__(self, x, w, scale, shift, skip=None):
-        self.x, self.w, self.scale, self.shift, self.skip = x, w, scale, shift, skip
-
-    def params(self, device):
-        from mvn_rocm import v2v
-        assert bool((self.w.bfloat16().float() == self.w).all())
-        return (v2v.pack_upsample_deep_weight(self.w.double()).to(device), self.scale.to(device), self.shift.to(device))
-
-    def run(self, device, x_dev=None, skip_dev=None):
-        from mvn_rocm import v2v
-        xd = cl(self.x, device) if x_dev is None else x_dev
-        sd = skip_dev if skip_dev is not None else (cl(self.skip, device) if self.skip is not None else None)
-        return v2v.upsample2_add_deep(xd, self.params(device), sd)
-
-    def pre_round(self, exact=True):
-        """(pre, u + skip) of the contract in float64: acc in f32 on the CPU when ``exact`` (sums of
-        at most 128 integer products), else in float64."""
-        if exact:
-            finite = torch.where(torch.isfinite(self.x), self.x, torch.zeros_like(self.x))
-            assert float(F.conv_transpose3d(finite.abs(), self.w.abs(), None, stride=2).max()) < 2.0 ** 24
-            acc = F.conv_transpose3d(self.x, self.w, None, stride=2).double()
-        else:
-            acc = F.conv_transpose3d(self.x.double(), self.w.double(), None, stride=2)
-        pre = acc * per_channel(self.scale) + per_channel(self.shift)
-        u = torch.where(pre <= 0, torch.zeros_like(pre), pre)
-        return pre, (u + self.skip.double() if self.skip is not None else u)
-
-    def reference(self):
-        pre, r = self.pre_round()
-        return r.float().bfloat16(), pre
-
-
-def up_integer_case(B, D, cout, seed, negative_pre):
-    """Integers in [-4, 4]: sums stay <= 128 * 16.  ``negative_pre``: every scale negative and the
-    shift non-positive with non-negative products, so every pre-activation is <= 0 while the skip
-    is positive: a ReLU after the add would give pre + skip, the contract gives skip."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(-4, 5, (B, 128, D, D, D), generator=g).float()
-    w = torch.randint(-4, 5, (128, cout, 2, 2, 2), generator=g).float()
-    scale, shift = exact_scale_shift(seed + 1, cout)
-    skip = torch.randint(-4, 5, (B, cout, 2 * D, 2 * D, 2 * D), generator=g).float()
-    if negative_pre:
-        x, w = x.abs(), w.abs()                                  # acc >= 0
-        scale, shift = -scale.abs(), -shift.abs()                # pre <= 0
-        skip = skip.abs() + 1.0                                  # skip > 0
-    return UpCase(x, w, scale, shift, skip)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("negative_pre", (False, True), ids=("mixed", "negative_pre_positive_skip"))
 @pytest.mark.parametrize("cout", (64, 128))
@@ -672,17 +488,12 @@ def test_deep_block_equals_the_two_launches(device, cin):
     assert err <= 2.0 ** -6                 # as the 32- and 64-channel blocks: two bf16 roundings deep
     empty = torch.zeros((0, D, D, D, cin), dtype=torch.bfloat16, device=device)
     assert tuple(v2v.res3d_block_deep(empty, p).shape) == (0, D, D, D, CO)
-    up = v2v.fold_upsample_block_deep(randomise(_upsample(128, 64), seed=3), device=device)
+    up = v2v.fold_upsample_block_deep(randomise(Upsample3DBlock(128, 64), seed=3), device=device)
     assert tuple(v2v.upsample2_add_deep(torch.zeros((0, D, D, D, 128), dtype=torch.bfloat16, device=device), up).shape) \
         == (0, 2 * D, 2 * D, 2 * D, 64)
     view = x.bfloat16().to(device).permute(0, 2, 3, 4, 1)       # NCDHW storage: copied
     assert not view.is_contiguous()
     assert_same_bits(v2v.res3d_block_deep(view, p), two)
-
-
-def _upsample(cin, cout):
-    from test_gpu_v2v_res3d import Upsample3DBlock
-    return Upsample3DBlock(cin, cout)
 
 
 @pytest.mark.gpu
@@ -700,46 +511,6 @@ def test_deep_two_calls_give_the_same_bits(device):
 
 
 # ----------------------------------------------------------------------------- wiring
-def chain_deep(m, vol_cl):
-    """V2VEval(half_res="kernels", deep="kernels").trunk written out from the public functions."""
-    from mvn_rocm import v2v
-    dev = vol_cl.device
-    fl, ed = m.front_layers, m.encoder_decoder
-    c0, b0 = fl[0].block[0], fl[0].block[1]
-    h = v2v.v2v_front(vol_cl, *v2v.fold_basic3d_block(c0.weight, c0.bias, b0.weight, b0.bias, b0.running_mean,
-                                                      b0.running_var, b0.eps, device=dev), torch.bfloat16)
-    h = h.permute(0, 2, 3, 4, 1).contiguous()
-    for i in (1, 2, 3):
-        h = v2v.res3d_block(h, v2v.fold_res3d_block(fl[i], device=dev))
-
-    def wide(name, x):
-        return v2v.res3d_block_wide(x, v2v.fold_res3d_block_wide(getattr(ed, name), device=dev))
-
-    def deep(name, x):
-        return v2v.res3d_block_deep(x, v2v.fold_res3d_block_deep(getattr(ed, name), device=dev))
-
-    def up(name, x, skip):
-        return v2v.upsample2_add_deep(x, v2v.fold_upsample_block_deep(getattr(ed, name), device=dev), skip)
-
-    s1 = v2v.res3d_block(h, v2v.fold_res3d_block(ed.skip_res1, device=dev))
-    e1 = wide("encoder_res1", v2v.max_pool2_cl(h))
-    s2 = wide("skip_res2", e1)
-    x = deep("encoder_res2", v2v.max_pool2_cl(e1))
-    s3 = deep("skip_res3", x)
-    x = deep("encoder_res3", v2v.max_pool2_cl(x))
-    s4 = deep("skip_res4", x)
-    x = deep("encoder_res4", v2v.max_pool2_cl(x))
-    s5 = deep("skip_res5", x)
-    x = deep("mid_res", deep("encoder_res5", v2v.max_pool2_cl(x)))
-    assert tuple(x.shape[1:]) == (1, 1, 1, 128) and tuple(s5.shape[1:4]) == (2, 2, 2)
-    x = up("decoder_upsample5", deep("decoder_res5", x), s5)
-    x = up("decoder_upsample4", deep("decoder_res4", x), s4)
-    x = up("decoder_upsample3", deep("decoder_res3", x), s3)
-    x = up("decoder_upsample2", deep("decoder_res2", x), s2)
-    x = v2v.upsample2_add(wide("decoder_res1", x), v2v.fold_upsample_block(ed.decoder_upsample1, device=dev), s1)
-    return v2v.res3d_block(x, v2v.fold_res3d_block(m.back_layers[0], device=dev))
-
-
 @pytest.mark.gpu
 def test_v2veval_deep_wiring(device):
     """V = 32, B = 2, the stand-in model (deep extents 8, 4, 2, 1): with deep="kernels" trunk equals

@@ -21,23 +21,13 @@ import torch
 from torch import nn
 
 from conftest import assert_bits_equal, max_rel
+from v2v_kit import Basic3DBlock
 
 TIGHT, LOOSE, CAP = 1e-4, 2.0 ** -8, 0.005
 C = 32
 
 
 # ---------------------------------------------------------------- stand-ins and the restatement
-class Basic3DBlock(nn.Module):
-    """The reference's Basic3DBlock (v2v.py:7-17), from torch.nn."""
-
-    def __init__(self, cin, cout, k):
-        super().__init__()
-        self.block = nn.Sequential(nn.Conv3d(cin, cout, k, 1, (k - 1) // 2), nn.BatchNorm3d(cout), nn.ReLU(True))
-
-    def forward(self, x):
-        return self.block(x)
-
-
 def make_head(J, seed, dead_channel=False):
     """(block1, block2, output_conv) in eval mode: Xavier-normal weights (v2v.py:171-176), small
     biases, BatchNorm statistics of a trained layer's order of magnitude.  ``dead_channel``: the

@@ -59,7 +59,8 @@ import torch
 from torch import nn
 
 from conftest import assert_bits_equal
-from test_gpu_v2v_head import Basic3DBlock, C, LAYOUTS, as_layout, run_head
+from test_gpu_v2v_head import C, LAYOUTS, as_layout, run_head
+from v2v_kit import Basic3DBlock
 
 DTYPES = (torch.float32, torch.bfloat16)
 JS = (1, 4, 15, 16, 17, 31, 32)

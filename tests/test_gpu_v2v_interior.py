@@ -2,28 +2,33 @@
 pool, the 64-channel 3x3x3 conv + folded BN + skip + ReLU, the fused upsample + skip add, the wide
 block and V2VEval(half_res="kernels") (MI355X only).
 
-The method is tests/test_gpu_v2v_res3d.py's: operands for which the kernel's f32 arithmetic is
-exact in any summation order (integers in [-4, 4], power-of-two scales, shifts in quarters; impulse
+The method is tests/v2v_kit.py's, on its 64-channel record: operands for which the kernel's f32
+arithmetic is exact in any summation order (integers in [-4, 4], power-of-two scales, shifts in quarters; impulse
 lattices with one product per output), compared bit for bit with the arithmetic contract of
 include/mvn_hip.h restated in float64, plus random data against that restatement with the
 contract's own bound.  Reads nothing outside the repository.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from conftest import assert_parity_with_nans
-from test_gpu_v2v_res3d import (E2E_MULT, E2E_SIDE, IDENTITY, NONE, POINTWISE, Res3DBlock,
-                                assert_same_bits, banded, bands_intact, bf16_full, bf16_operand_model, bf16r, bits,
-                                box_mask, chain, cl, e2e_case, lattice_reference, ncdhw, per_channel, randomise,
-                                stand_in_model, BAND, INF_VOXELS, NAN_VOXELS, N_BOX)
+from v2v_kit import (BAND, E2E_MULT, E2E_SIDE, IDENTITY, INF_VOXELS, MODE_NAME, N_BOX, NAN_VOXELS, NONE, POINTWISE,
+                     UP_WIDE, WIDE, Res3DBlock, assert_same_bits, banded, bands_intact, bf16_full, bf16_operand_model, bf16r,
+                     bits, box_mask, chain, chain_kernels, check_bound, cl, e2e_case, lattice_input, lattice_reference, ncdhw,
+                     per_channel, randomise, stand_in_model)
 
 CO = 64
 SKIP_C = {NONE: 0, IDENTITY: 64, POINTWISE: 32}
-MODE_NAME = {NONE: "none", IDENTITY: "identity", POINTWISE: "pointwise"}
+# the method of tests/v2v_kit.py on the 64-channel level and its upsample
+WideCase, pack_wide, exact_scale_shift = WIDE.case, WIDE.pack, WIDE.exact_scale_shift
+integer_case, parity_case, random_case = WIDE.integer_case, WIDE.parity_case, WIDE.random_case
+UpCase = UP_WIDE.case
+
+
+def up_integer_case(B, V, seed, negative_pre):
+    return UP_WIDE.integer_case(B, V, 32, seed, negative_pre)
 
 
 # ----------------------------------------------------------------------------- pool
@@ -103,90 +108,6 @@ def test_pool_empty_batch_and_noncontiguous_input(device):
     assert (bits(v2v.max_pool2_cl(view)) == pool_reference_bits(view.contiguous())).all()
 
 
-# ----------------------------------------------------------------------------- wide conv: helpers
-def exact_scale_shift(seed, n=CO):
-    """Per-channel scale = +-2^k (k in -2..1, both signs present) and shift = a multiple of 1/4."""
-    g = torch.Generator().manual_seed(seed)
-    k = torch.randint(-2, 2, (n,), generator=g).float()
-    sign = torch.where(torch.arange(n) % 3 == 1, -1.0, 1.0)
-    shift = torch.randint(-8, 9, (n,), generator=g).float() / 4 + 0.0
-    assert not bool((torch.signbit(shift) & (shift == 0)).any())
-    return sign * torch.exp2(k), shift
-
-
-def pack_wide(w, device):
-    from mvn_rocm import v2v
-    assert bool((w.bfloat16().float() == w).all())
-    return v2v.pack_conv3_wide_weight(w.double()).to(device)
-
-
-class WideCase:
-    """Operands of one mvn_v2v_conv3_wide launch on the CPU (f32 tensors holding bf16-exact values)."""
-
-    def __init__(self, x, w, scale, shift, mode=NONE, skip=None, ws=None, scale_s=None, shift_s=None):
-        self.x, self.w, self.scale, self.shift, self.mode = x, w, scale, shift, mode
-        self.skip, self.ws, self.scale_s, self.shift_s = skip, ws, scale_s, shift_s
-
-    def args(self, device, x_dev=None, skip_dev=None):
-        from mvn_rocm import v2v
-        a = [cl(self.x, device) if x_dev is None else x_dev, pack_wide(self.w, device), self.scale.to(device),
-             self.shift.to(device)]
-        if self.mode != NONE:
-            a.append(cl(self.skip, device) if skip_dev is None else skip_dev)
-        if self.mode == POINTWISE:
-            a += [v2v.pack_pointwise_skip_wide_weight(self.ws.double()).to(device), self.scale_s.to(device),
-                  self.shift_s.to(device)]
-        return a
-
-    def run(self, device, x_dev=None, skip_dev=None):
-        from mvn_rocm import v2v
-        return v2v.v2v_conv3_wide(*self.args(device, x_dev, skip_dev))
-
-    def pre_relu(self, exact=True):
-        """r of the contract in float64; the convs in f32 on the CPU when ``exact`` (guarded: exact
-        for these operands), else in float64."""
-        x, w = self.x, self.w
-        if exact:
-            finite = torch.where(torch.isfinite(x), x, torch.zeros_like(x))
-            assert float(F.conv3d(finite.abs(), w.abs(), None, padding=1).max()) < 2.0 ** 24
-            acc = F.conv3d(x, w, None, padding=1).double()
-        else:
-            acc = F.conv3d(x.double(), w.double(), None, padding=1)
-        r = acc * per_channel(self.scale) + per_channel(self.shift)
-        if self.mode == IDENTITY:
-            r = r + self.skip.double()
-        elif self.mode == POINTWISE:
-            w1 = self.ws.view(CO, 32, 1, 1, 1)
-            acc_s = F.conv3d(self.skip, w1).double() if exact else F.conv3d(self.skip.double(), w1.double())
-            r = r + (acc_s * per_channel(self.scale_s) + per_channel(self.shift_s))
-        return r
-
-    def reference(self):
-        r = self.pre_relu()
-        assert not bool((torch.signbit(r) & (r == 0)).any()), "the pre-relu reference holds a -0"
-        return torch.where(r <= 0, torch.zeros_like(r), r).float().bfloat16(), r
-
-
-def integer_case(B, V, cin, mode, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(-4, 5, (B, cin, V, V, V), generator=g).float()
-    w = torch.randint(-4, 5, (CO, cin, 3, 3, 3), generator=g).float()
-    case = WideCase(x, w, *exact_scale_shift(seed + 1), mode)
-    if mode != NONE:
-        case.skip = torch.randint(-4, 5, (B, SKIP_C[mode], V, V, V), generator=g).float()
-    if mode == POINTWISE:
-        case.ws = torch.randint(-4, 5, (CO, 32), generator=g).float()
-        case.scale_s, case.shift_s = exact_scale_shift(seed + 2)
-    return case
-
-
-@functools.lru_cache(maxsize=None)
-def parity_case(B, V, cin, mode):
-    case = integer_case(B, V, cin, mode, seed=1000 * B + V + 7 * cin + mode)
-    ref, r = case.reference()
-    return case, ref, r
-
-
 # (cin, mode): the issue's four and the one Res3DBlock(32, 64)'s second conv takes
 WIDE_KINDS = ((32, NONE), (32, POINTWISE), (64, NONE), (64, IDENTITY), (64, POINTWISE))
 WIDE_IDS = [f"{c}_{MODE_NAME[m]}" for c, m in WIDE_KINDS]
@@ -237,19 +158,6 @@ def test_wide_whole_column_walk(device):
 
 # ----------------------------------------------------------------------------- wide conv: impulses
 LATTICE_B, LATTICE_V, LATTICE_OFFS = 2, 16, (0, 2)
-
-
-def lattice_input(cin, off, g):
-    """Impulses at the voxels off, off + 3, ... of every axis, one channel each."""
-    B, V = LATTICE_B, LATTICE_V
-    x = torch.zeros((B, cin, V, V, V))
-    pts = torch.arange(off, V, 3)
-    n = pts.numel()
-    ch = (torch.arange(B * n ** 3).view(B, n, n, n) * 5 + 11 * torch.arange(B).view(B, 1, 1, 1)) % cin
-    sub = torch.zeros(B, cin, n, n, n).scatter_(1, ch.unsqueeze(1), bf16_full((B, 1, n, n, n), g))
-    x[:, :, off::3, off::3, off::3] = sub
-    assert int((x != 0).sum()) == B * n ** 3 and len(set(ch.flatten().tolist())) == cin      # every channel used
-    return x
 
 
 @pytest.mark.parametrize("cin", (32, 64))
@@ -464,44 +372,6 @@ def test_wide_no_reads_or_writes_outside_the_tensors(device, cin, mode):
 
 
 # ----------------------------------------------------------------------------- wide conv: random data
-def random_case(B, V, cin, mode, seed, x=None):
-    g = torch.Generator().manual_seed(seed)
-    if x is None:
-        x = bf16r(torch.randn(B, cin, V, V, V, generator=g))
-    w = bf16r(torch.randn(CO, cin, 3, 3, 3, generator=g) * (2.0 / (27 * (cin + CO))) ** 0.5 * 3)
-    scale = (0.75 + 0.5 * torch.rand(CO, generator=g)) * torch.where(torch.arange(CO) % 5 == 2, -1.0, 1.0)
-    case = WideCase(x, w, scale, 0.2 * torch.randn(CO, generator=g), mode)
-    if mode != NONE:
-        case.skip = bf16r(torch.randn(B, SKIP_C[mode], V, V, V, generator=g))
-    if mode == POINTWISE:
-        case.ws = bf16r(torch.randn(CO, 32, generator=g) * 0.2)
-        case.scale_s = 0.75 + 0.5 * torch.rand(CO, generator=g)
-        case.shift_s = 0.2 * torch.randn(CO, generator=g)
-    return case
-
-
-def check_bound(case, got, what):
-    """|got - ref| <= 2^-8 |ref| + gamma S per element, gamma = (27 Cin + Cin_skip + 4) 2^-24 (half a
-    bf16 ulp plus the worst-case f32 summation bound of the contract), ref the
-    float64 restatement; returns the worst fraction of the bar."""
-    cin = case.x.shape[1]
-    gamma = (27 * cin + SKIP_C[case.mode] + 4) * 2.0 ** -24
-    r = case.pre_relu(exact=False)
-    ref = torch.where(r <= 0, torch.zeros_like(r), r)
-    S = F.conv3d(case.x.double().abs(), case.w.double().abs(), None, padding=1) * per_channel(case.scale).abs() \
-        + per_channel(case.shift).abs()
-    if case.mode == IDENTITY:
-        S = S + case.skip.double().abs()
-    elif case.mode == POINTWISE:
-        S = S + F.conv3d(case.skip.double().abs(), case.ws.double().abs().view(CO, 32, 1, 1, 1)) \
-            * per_channel(case.scale_s).abs() + per_channel(case.shift_s).abs()
-    bar = 2.0 ** -8 * ref.abs() + gamma * S
-    frac = float(((got.double() - ref).abs() / bar).max())
-    print(f"{what}: worst |got - ref| / bar = {frac:.4f}")
-    assert frac <= 1.0
-    return frac
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin,mode", ((32, POINTWISE), (64, IDENTITY)), ids=("32to64_pointwise", "64to64_identity"))
 @pytest.mark.parametrize("V", (16, 32))
@@ -521,56 +391,6 @@ def test_wide_random_data_against_float64_restatement(device, V, cin, mode):
 
 
 # ----------------------------------------------------------------------------- upsample
-class UpCase:
-    """Operands of one mvn_v2v_upsample2 launch on the CPU (f32 tensors of bf16-exact values)."""
-
-    def __init__(self, x, w, scale, shift, skip=None):
-        self.x, self.w, self.scale, self.shift, self.skip = x, w, scale, shift, skip
-
-    def params(self, device):
-        from mvn_rocm import v2v
-        assert bool((self.w.bfloat16().float() == self.w).all())
-        return (v2v.pack_upsample_weight(self.w.double()).to(device), self.scale.to(device), self.shift.to(device))
-
-    def run(self, device, x_dev=None, skip_dev=None):
-        from mvn_rocm import v2v
-        xd = cl(self.x, device) if x_dev is None else x_dev
-        sd = skip_dev if skip_dev is not None else (cl(self.skip, device) if self.skip is not None else None)
-        return v2v.upsample2_add(xd, self.params(device), sd)
-
-    def pre_round(self, exact=True):
-        """(pre, u + skip) of the contract in float64: acc in f32 on the CPU when ``exact`` (sums of
-        at most 64 integer products), else in float64."""
-        if exact:
-            acc = F.conv_transpose3d(self.x, self.w, None, stride=2).double()
-        else:
-            acc = F.conv_transpose3d(self.x.double(), self.w.double(), None, stride=2)
-        pre = acc * per_channel(self.scale) + per_channel(self.shift)
-        u = torch.where(pre <= 0, torch.zeros_like(pre), pre)
-        return pre, (u + self.skip.double() if self.skip is not None else u)
-
-    def reference(self):
-        pre, r = self.pre_round()
-        return r.float().bfloat16(), pre
-
-
-def up_integer_case(B, V, seed, negative_pre):
-    """Integers in [-4, 4]: sums stay <= 64 * 16.  ``negative_pre``: every scale negative and the
-    shift non-positive where the weights allow a positive sum, so most pre-activations are <= 0
-    while the skip is positive: a ReLU after the add would give pre + skip, the contract gives
-    skip."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(-4, 5, (B, 64, V, V, V), generator=g).float()
-    w = torch.randint(-4, 5, (64, 32, 2, 2, 2), generator=g).float()
-    scale, shift = exact_scale_shift(seed + 1, 32)
-    skip = torch.randint(-4, 5, (B, 32, 2 * V, 2 * V, 2 * V), generator=g).float()
-    if negative_pre:
-        x, w = x.abs(), w.abs()                                  # acc >= 0
-        scale, shift = -scale.abs(), -shift.abs()                # pre <= 0
-        skip = skip.abs() + 1.0                                  # skip > 0
-    return UpCase(x, w, scale, shift, skip)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("negative_pre", (False, True), ids=("mixed", "negative_pre_positive_skip"))
 @pytest.mark.parametrize("B,V", ((1, 16), (3, 16), (1, 32)))
@@ -726,28 +546,6 @@ def test_wide_block_equals_the_two_launches(device, cin):
 
 
 # ----------------------------------------------------------------------------- wiring
-def chain_kernels(m, ev, vol_cl):
-    """V2VEval(half_res="kernels").trunk written out from the public functions."""
-    from mvn_rocm import v2v
-    dev = vol_cl.device
-    fl, ed = m.front_layers, m.encoder_decoder
-    h = v2v.v2v_front(vol_cl, *v2v.fold_basic3d_block(fl[0].block[0].weight, fl[0].block[0].bias, fl[0].block[1].weight,
-                                                      fl[0].block[1].bias, fl[0].block[1].running_mean,
-                                                      fl[0].block[1].running_var, fl[0].block[1].eps, device=dev),
-                      torch.bfloat16)
-    h = h.permute(0, 2, 3, 4, 1).contiguous()
-    for i in (1, 2, 3):
-        h = v2v.res3d_block(h, v2v.fold_res3d_block(fl[i], device=dev))
-    s1 = v2v.res3d_block(h, v2v.fold_res3d_block(ed.skip_res1, device=dev))
-    e1 = v2v.res3d_block_wide(v2v.max_pool2_cl(h), v2v.fold_res3d_block_wide(ed.encoder_res1, device=dev))
-    s2 = v2v.res3d_block_wide(e1, v2v.fold_res3d_block_wide(ed.skip_res2, device=dev))
-    d = v2v.v2v_interior_deep(ev.interior, e1.permute(0, 4, 1, 2, 3).float())
-    d = (d + s2.permute(0, 4, 1, 2, 3)).permute(0, 2, 3, 4, 1).to(torch.bfloat16).contiguous()
-    d1 = v2v.res3d_block_wide(d, v2v.fold_res3d_block_wide(ed.decoder_res1, device=dev))
-    x = v2v.upsample2_add(d1, v2v.fold_upsample_block(ed.decoder_upsample1, device=dev), s1)
-    return v2v.res3d_block(x, v2v.fold_res3d_block(m.back_layers[0], device=dev))
-
-
 @pytest.mark.gpu
 def test_v2veval_half_res_wiring(device):
     """V = 32, B = 2, the stand-in model: with half_res="kernels" trunk equals the chain written out

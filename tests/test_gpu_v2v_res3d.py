@@ -13,265 +13,28 @@ order, and compare bits (as tests/test_gpu_v2v_front_edges.py does for the front
 
 The reference is r in float64 per the arithmetic contract of mvn_v2v_conv3 (include/mvn_hip.h),
 +0 where r <= 0 (NaN kept), cast to f32, then ``.bfloat16()``; the tests assert r holds no -0.
+The case builders, the reference and the bound are tests/v2v_kit.py's, on its 32-channel record.
 
 Tiles are 4 x 8 x 16 (x, y, z); a block walks a column of V / 4 tiles along x through a ring of
 6 x-slices whose slot pattern repeats every 3 tiles; the grid is B * (V / 8) * (V / 16) blocks.
 Reads nothing outside the repository.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
-from torch import nn
 
 from conftest import assert_parity_with_nans
+from v2v_kit import (BAND, E2E_MULT, E2E_SIDE, IDENTITY, INF_VOXELS, J, N_BOX, NAN_VOXELS, NONE, POINTWISE, RES3D,
+                     Res3DBlock, assert_same_bits, banded, bands_intact, bf16_full, bf16_operand_model, bf16r, bits,
+                     box_mask, chain, check_bound, cl, e2e_case, lattice_reference, ncdhw, randomise, stand_in_model)
 
 CO = 32
-NONE, IDENTITY, POINTWISE = 0, 1, 2
 MODES = {"none": NONE, "identity": IDENTITY, "pointwise": POINTWISE}
 SKIP_C = {NONE: 0, IDENTITY: 32, POINTWISE: 16}
-
-
-# ----------------------------------------------------------------------------- stand-ins
-class Basic3DBlock(nn.Module):
-    """The reference's Basic3DBlock (v2v.py:7-17), from torch.nn."""
-
-    def __init__(self, cin, cout, k):
-        super().__init__()
-        self.block = nn.Sequential(nn.Conv3d(cin, cout, k, 1, (k - 1) // 2), nn.BatchNorm3d(cout), nn.ReLU(True))
-
-    def forward(self, x):
-        return self.block(x)
-
-
-class Res3DBlock(nn.Module):
-    """The reference's Res3DBlock (v2v.py:20-42), from torch.nn, with its attribute names."""
-
-    def __init__(self, cin, cout, bias=True):
-        super().__init__()
-        self.res_branch = nn.Sequential(nn.Conv3d(cin, cout, 3, 1, 1, bias=bias), nn.BatchNorm3d(cout), nn.ReLU(True),
-                                        nn.Conv3d(cout, cout, 3, 1, 1, bias=bias), nn.BatchNorm3d(cout))
-        self.skip_con = nn.Sequential() if cin == cout else nn.Sequential(nn.Conv3d(cin, cout, 1, 1, 0, bias=bias),
-                                                                          nn.BatchNorm3d(cout))
-
-    def forward(self, x):
-        return F.relu(self.res_branch(x) + self.skip_con(x), True)
-
-
-class Pool3DBlock(nn.Module):
-    def __init__(self, k):
-        super().__init__()
-        self.k = k
-
-    def forward(self, x):
-        return F.max_pool3d(x, kernel_size=self.k, stride=self.k)
-
-
-class Upsample3DBlock(nn.Module):
-    def __init__(self, cin, cout):
-        super().__init__()
-        self.block = nn.Sequential(nn.ConvTranspose3d(cin, cout, 2, 2), nn.BatchNorm3d(cout), nn.ReLU(True))
-
-    def forward(self, x):
-        return self.block(x)
-
-
-class EncoderDecorder(nn.Module):
-    """The reference's EncoderDecorder (v2v.py:69-138): attribute names and forward."""
-
-    def __init__(self):
-        super().__init__()
-        self.encoder_pool1, self.encoder_res1 = Pool3DBlock(2), Res3DBlock(32, 64)
-        self.encoder_pool2, self.encoder_res2 = Pool3DBlock(2), Res3DBlock(64, 128)
-        self.encoder_pool3, self.encoder_res3 = Pool3DBlock(2), Res3DBlock(128, 128)
-        self.encoder_pool4, self.encoder_res4 = Pool3DBlock(2), Res3DBlock(128, 128)
-        self.encoder_pool5, self.encoder_res5 = Pool3DBlock(2), Res3DBlock(128, 128)
-        self.mid_res = Res3DBlock(128, 128)
-        self.decoder_res5, self.decoder_upsample5 = Res3DBlock(128, 128), Upsample3DBlock(128, 128)
-        self.decoder_res4, self.decoder_upsample4 = Res3DBlock(128, 128), Upsample3DBlock(128, 128)
-        self.decoder_res3, self.decoder_upsample3 = Res3DBlock(128, 128), Upsample3DBlock(128, 128)
-        self.decoder_res2, self.decoder_upsample2 = Res3DBlock(128, 128), Upsample3DBlock(128, 64)
-        self.decoder_res1, self.decoder_upsample1 = Res3DBlock(64, 64), Upsample3DBlock(64, 32)
-        self.skip_res1, self.skip_res2 = Res3DBlock(32, 32), Res3DBlock(64, 64)
-        self.skip_res3, self.skip_res4, self.skip_res5 = Res3DBlock(128, 128), Res3DBlock(128, 128), Res3DBlock(128, 128)
-
-    def forward(self, x):
-        s1 = self.skip_res1(x)
-        x = self.encoder_res1(self.encoder_pool1(x))
-        s2 = self.skip_res2(x)
-        x = self.encoder_res2(self.encoder_pool2(x))
-        s3 = self.skip_res3(x)
-        x = self.encoder_res3(self.encoder_pool3(x))
-        s4 = self.skip_res4(x)
-        x = self.encoder_res4(self.encoder_pool4(x))
-        s5 = self.skip_res5(x)
-        x = self.encoder_res5(self.encoder_pool5(x))
-        x = self.mid_res(x)
-        x = self.decoder_upsample5(self.decoder_res5(x)) + s5
-        x = self.decoder_upsample4(self.decoder_res4(x)) + s4
-        x = self.decoder_upsample3(self.decoder_res3(x)) + s3
-        x = self.decoder_upsample2(self.decoder_res2(x)) + s2
-        return self.decoder_upsample1(self.decoder_res1(x)) + s1
-
-
-class V2VModel(nn.Module):
-    """The reference's V2VModel (v2v.py:141-169): attribute names and forward."""
-
-    def __init__(self, cin, J):
-        super().__init__()
-        self.front_layers = nn.Sequential(Basic3DBlock(cin, 16, 7), Res3DBlock(16, 32), Res3DBlock(32, 32),
-                                          Res3DBlock(32, 32))
-        self.encoder_decoder = EncoderDecorder()
-        self.back_layers = nn.Sequential(Res3DBlock(32, 32), Basic3DBlock(32, 32, 1), Basic3DBlock(32, 32, 1))
-        self.output_layer = nn.Conv3d(32, J, 1)
-
-    def forward(self, x):
-        return self.output_layer(self.back_layers(self.encoder_decoder(self.front_layers(x))))
-
-
-def randomise(module, seed, bias=0.1):
-    """Xavier-normal conv weights (v2v.py:171-180), small biases, BatchNorm statistics of a
-    trained layer's order of magnitude; eval mode."""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for m in module.modules():
-            if isinstance(m, (nn.Conv3d, nn.ConvTranspose3d)):
-                rf = m.weight[0, 0].numel()
-                fan = (m.weight.shape[0] + m.weight.shape[1]) * rf
-                m.weight.copy_(torch.randn(m.weight.shape, generator=g) * (2.0 / fan) ** 0.5)
-                if m.bias is not None:
-                    m.bias.copy_(torch.randn(m.bias.shape, generator=g) * bias)
-            elif isinstance(m, nn.BatchNorm3d):
-                n = m.num_features
-                m.weight.copy_(0.75 + 0.5 * torch.rand(n, generator=g))
-                m.bias.copy_(0.2 * torch.randn(n, generator=g))
-                m.running_mean.copy_(0.2 * torch.randn(n, generator=g))
-                m.running_var.copy_(0.75 + 0.5 * torch.rand(n, generator=g))
-    return module.eval()
-
-
-# ----------------------------------------------------------------------------- helpers
-def bits(t):
-    """The bit pattern of a bf16 / f32 tensor as a numpy unsigned array (on the host)."""
-    t = t.detach().cpu().contiguous()
-    if t.dtype == torch.float32:
-        return t.view(torch.int32).numpy().view(np.uint32)
-    assert t.dtype == torch.bfloat16
-    return t.view(torch.int16).numpy().view(np.uint16)
-
-
-def assert_same_bits(got, want):
-    a, b = bits(got), bits(want)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    bad = a != b
-    assert not bad.any(), f"{int(bad.sum())} of {bad.size} elements differ in their bits"
-
-
-def cl(x, device):
-    """(B, C, V, V, V) f32 holding bf16-exact values -> the kernel's (B, V, V, V, C) bf16 volume."""
-    xb = x.bfloat16()
-    assert bool(((xb.float() == x) | torch.isnan(x)).all()), "the test's volume is not exact in bf16"
-    return xb.permute(0, 2, 3, 4, 1).contiguous().to(device)
-
-
-def ncdhw(y_cl):
-    """The kernel's (B, V, V, V, 32) result as (B, 32, V, V, V) on the CPU."""
-    return y_cl.cpu().permute(0, 4, 1, 2, 3).contiguous()
-
-
-def pack3(w, device):
-    from mvn_rocm import v2v
-    assert bool((w.bfloat16().float() == w).all())
-    return v2v.pack_conv3_weight(w.double()).to(device)
-
-
-def packs(ws, device):
-    from mvn_rocm import v2v
-    return v2v.pack_pointwise_skip_weight(ws.double()).to(device)
-
-
-def exact_scale_shift(seed):
-    """Per-channel scale = +-2^k (k in -2..1, both signs present) and shift = a multiple of 1/4
-    (never -0)."""
-    g = torch.Generator().manual_seed(seed)
-    k = torch.randint(-2, 2, (CO,), generator=g).float()
-    sign = torch.where(torch.arange(CO) % 3 == 1, -1.0, 1.0)
-    scale = sign * torch.exp2(k)
-    shift = torch.randint(-8, 9, (CO,), generator=g).float() / 4 + 0.0
-    assert not bool((torch.signbit(shift) & (shift == 0)).any())
-    assert bool((scale < 0).any()) and bool((scale > 0).any())
-    return scale, shift
-
-
-def per_channel(t):
-    return t.double().view(1, -1, 1, 1, 1)
-
-
-class Case:
-    """Operands of one launch on the CPU (f32 tensors holding bf16-exact values)."""
-
-    def __init__(self, x, w, scale, shift, mode=NONE, skip=None, ws=None, scale_s=None, shift_s=None):
-        self.x, self.w, self.scale, self.shift, self.mode = x, w, scale, shift, mode
-        self.skip, self.ws, self.scale_s, self.shift_s = skip, ws, scale_s, shift_s
-
-    def run(self, device, x_dev=None, skip_dev=None):
-        from mvn_rocm import v2v
-        xd = cl(self.x, device) if x_dev is None else x_dev
-        args = [xd, pack3(self.w, device), self.scale.to(device), self.shift.to(device)]
-        if self.mode != NONE:
-            args.append(cl(self.skip, device) if skip_dev is None else skip_dev)
-        if self.mode == POINTWISE:
-            args += [packs(self.ws, device), self.scale_s.to(device), self.shift_s.to(device)]
-        return v2v.v2v_conv3(*args)
-
-    def pre_relu(self, exact=True):
-        """r of the contract in float64; the conv in f32 on the CPU when ``exact`` (guarded: exact
-        for these operands), else in float64."""
-        x, w = self.x, self.w
-        if exact:
-            finite = torch.where(torch.isfinite(x), x, torch.zeros_like(x))
-            assert float(F.conv3d(finite.abs(), w.abs(), None, padding=1).max()) < 2.0 ** 24
-            acc = F.conv3d(x, w, None, padding=1).double()
-        else:
-            acc = F.conv3d(x.double(), w.double(), None, padding=1)
-        r = acc * per_channel(self.scale) + per_channel(self.shift)
-        if self.mode == IDENTITY:
-            r = r + self.skip.double()
-        elif self.mode == POINTWISE:
-            w1 = self.ws.view(CO, 16, 1, 1, 1)
-            acc_s = F.conv3d(self.skip, w1).double() if exact else F.conv3d(self.skip.double(), w1.double())
-            r = r + (acc_s * per_channel(self.scale_s) + per_channel(self.shift_s))
-        return r
-
-    def reference(self):
-        """(bf16 reference, float64 pre-relu r)."""
-        r = self.pre_relu()
-        assert not bool((torch.signbit(r) & (r == 0)).any()), "the pre-relu reference holds a -0"
-        y = torch.where(r <= 0, torch.zeros_like(r), r)            # a NaN is neither: kept
-        return y.float().bfloat16(), r
-
-
-def integer_case(B, V, cin, mode, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randint(-4, 5, (B, cin, V, V, V), generator=g).float()
-    w = torch.randint(-4, 5, (CO, cin, 3, 3, 3), generator=g).float()
-    scale, shift = exact_scale_shift(seed + 1)
-    case = Case(x, w, scale, shift, mode)
-    if mode != NONE:
-        case.skip = torch.randint(-4, 5, (B, SKIP_C[mode], V, V, V), generator=g).float()
-    if mode == POINTWISE:
-        case.ws = torch.randint(-4, 5, (CO, 16), generator=g).float()
-        case.scale_s, case.shift_s = exact_scale_shift(seed + 2)
-    return case
-
-
-@functools.lru_cache(maxsize=None)
-def parity_case(B, V, cin, mode):
-    case = integer_case(B, V, cin, mode, seed=1000 * B + V + 7 * cin + mode)
-    ref, r = case.reference()
-    return case, ref, r
+# the method of tests/v2v_kit.py on the 32-channel level
+Case, pack3, packs, exact_scale_shift = RES3D.case, RES3D.pack, RES3D.pack_skip, RES3D.exact_scale_shift
+integer_case, parity_case, random_case = RES3D.integer_case, RES3D.parity_case, RES3D.random_case
 
 
 # ----------------------------------------------------------------------------- 1. exact parity
@@ -304,21 +67,6 @@ def test_exact_parity_integer_inputs(device, B, V, cin, mode):
 
 
 # ----------------------------------------------------------------------------- 2. impulse lattice
-def bf16_full(shape, g):
-    """Normal bf16 values with full 8-bit significands (random normal, rounded to bf16)."""
-    v = torch.randn(shape, generator=g).bfloat16().float()
-    return torch.where(v.abs() > 2.0 ** -100, v, torch.ones_like(v))
-
-
-def lattice_reference(x, w, scale, pad):
-    """At most one product per output (asserted), so the float64 conv IS that product: times
-    scale in float64, rounded once to f32 (the kernel's fma with a zero shift)."""
-    k = 2 * pad + 1
-    hits = F.conv3d((x != 0).double(), torch.ones(1, x.shape[1], k, k, k, dtype=torch.float64), padding=pad)
-    assert float(hits.max()) == 1.0
-    return (F.conv3d(x.double(), w.double(), None, padding=pad) * per_channel(scale)).float()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin", (16, 32))
 @pytest.mark.parametrize("B,V,off", ((2, 16, 0), (2, 16, 2), (1, 48, 1)))
@@ -398,52 +146,6 @@ def test_borders_are_zero_padding(device, cin):
 
 
 # ----------------------------------------------------------------------------- 4. random data
-def bf16r(t):
-    return t.float().bfloat16().float()
-
-
-def random_case(B, V, cin, mode, seed, x=None):
-    g = torch.Generator().manual_seed(seed)
-    if x is None:
-        x = bf16r(torch.randn(B, cin, V, V, V, generator=g))
-    w = bf16r(torch.randn(CO, cin, 3, 3, 3, generator=g) * (2.0 / (27 * (cin + CO))) ** 0.5 * 3)
-    scale = (0.75 + 0.5 * torch.rand(CO, generator=g)) * torch.where(torch.arange(CO) % 5 == 2, -1.0, 1.0)
-    shift = 0.2 * torch.randn(CO, generator=g)
-    case = Case(x, w, scale, shift, mode)
-    if mode != NONE:
-        case.skip = bf16r(torch.randn(B, SKIP_C[mode], V, V, V, generator=g))
-    if mode == POINTWISE:
-        case.ws = bf16r(torch.randn(CO, 16, generator=g) * 0.2)
-        case.scale_s = 0.75 + 0.5 * torch.rand(CO, generator=g)
-        case.shift_s = 0.2 * torch.randn(CO, generator=g)
-    return case
-
-
-def check_bound(case, got, what):
-    """|got - ref| <= 2^-8 |ref| + gamma S per element (half a bf16 ulp plus the worst-case f32
-    summation bound), ref the float64 restatement; returns the worst fraction of the bar.  The
-    same conv in f32 on the CPU must sit far inside gamma S (a bound, not a measurement)."""
-    cin = case.x.shape[1]
-    gamma = (27 * cin + SKIP_C[case.mode] + 4) * 2.0 ** -24
-    r = case.pre_relu(exact=False)
-    ref = torch.where(r <= 0, torch.zeros_like(r), r)
-    S = F.conv3d(case.x.double().abs(), case.w.double().abs(), None, padding=1) * per_channel(case.scale).abs() \
-        + per_channel(case.shift).abs()
-    if case.mode == IDENTITY:
-        S = S + case.skip.double().abs()
-    elif case.mode == POINTWISE:
-        S = S + F.conv3d(case.skip.double().abs(), case.ws.double().abs().view(CO, 16, 1, 1, 1)) \
-            * per_channel(case.scale_s).abs() + per_channel(case.shift_s).abs()
-    r32 = case.pre_relu(exact=True)                     # the f32 CPU conv (no exactness guard needed: finite data)
-    cpu_frac = float(((r32 - r).abs() / (gamma * S)).max())
-    bar = 2.0 ** -8 * ref.abs() + gamma * S
-    frac = float(((got.double() - ref).abs() / bar).max())
-    print(f"{what}: worst |got - ref| / bar = {frac:.4f}; f32 CPU conv at {cpu_frac:.4f} of gamma S")
-    assert cpu_frac <= 0.05, "the f32 CPU conv is not far inside gamma S: the bar is no bound for these inputs"
-    assert frac <= 1.0
-    return frac
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin,mode", ((16, POINTWISE), (32, IDENTITY)), ids=("16to32_pointwise", "32to32_identity"))
 @pytest.mark.parametrize("V", (16, 32))
@@ -463,20 +165,6 @@ def test_random_data_against_float64_restatement(device, V, cin, mode):
 
 
 # ----------------------------------------------------------------------------- 5. non-finite voxels
-# 3^3 boxes pairwise disjoint: both corners, either side of the x seam 11 | 12, of the y seam
-# 7 | 8 and of the z seam 15 | 16 (tiles are 4 x 8 x 16)
-NAN_VOXELS = ((0, 0, 0), (31, 31, 31), (11, 20, 5), (12, 20, 27), (24, 7, 8), (24, 8, 24), (20, 27, 15), (4, 27, 16))
-INF_VOXELS = ((12, 12, 12, 5, float("inf")), (22, 20, 7, 13, float("-inf")))      # x, y, z, channel, value
-N_BOX = 2 * 2 ** 3 + 6 * 3 ** 3
-
-
-def box_mask(V, voxels, pad):
-    m = np.zeros((V, V, V), bool)
-    for x, y, z in voxels:
-        m[max(x - pad, 0):x + pad + 1, max(y - pad, 0):y + pad + 1, max(z - pad, 0):z + pad + 1] = True
-    return m
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin", (16, 32))
 def test_nonfinite_input_voxels_follow_torch(device, cin):
@@ -543,29 +231,6 @@ def test_nonfinite_skip_voxels_reach_their_own_voxel(device, mode):
 
 
 # ----------------------------------------------------------------------------- 6. stray reads, writes
-SENTINEL = 0x7FA5            # a NaN with its own payload: relu of finite data never gives it
-BAND = 64 * 1024 // 2        # 64 KiB of bf16 on either side
-
-
-def banded(t, fill_nan=True):
-    """(the larger buffer, the view of ``t``'s shape inside it): NaN bands around an input,
-    sentinel bands (and sentinel contents) around an output when ``t`` is a shape."""
-    if isinstance(t, torch.Tensor):
-        big = torch.full((BAND + t.numel() + BAND,), float("nan"), dtype=torch.bfloat16, device=t.device)
-        view = big[BAND:BAND + t.numel()].view(t.shape)
-        view.copy_(t)
-        return big, view
-    shape, device = t
-    n = int(np.prod(shape))
-    big = torch.full((BAND + n + BAND,), SENTINEL, dtype=torch.int16, device=device)
-    return big, big[BAND:BAND + n].view(torch.bfloat16).view(shape)
-
-
-def bands_intact(big, n, inside_written):
-    ok = bool((big[:BAND] == SENTINEL).all()) and bool((big[BAND + n:] == SENTINEL).all())
-    return ok and (not inside_written or not bool((big[BAND:BAND + n] == SENTINEL).any()))
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin,mode", ((32, IDENTITY), (16, POINTWISE)), ids=("identity", "pointwise"))
 def test_no_reads_or_writes_outside_the_tensors(device, cin, mode):
@@ -720,32 +385,6 @@ def test_empty_batch_and_noncontiguous_input(device):
 
 
 # ----------------------------------------------------------------------------- 9, 10. V2VEval
-J = 17
-
-
-@functools.lru_cache(maxsize=None)
-def stand_in_model():
-    return randomise(V2VModel(32, J), seed=2024, bias=0.02)
-
-
-def chain(m, ev, vol_cl):
-    """V2VEval.trunk written out from the public pieces and the stand-in's own modules."""
-    from mvn_rocm import v2v
-    dev = vol_cl.device
-    fl, ed = m.front_layers, m.encoder_decoder
-    h = v2v.v2v_front(vol_cl, *v2v.fold_basic3d_block(fl[0].block[0].weight, fl[0].block[0].bias, fl[0].block[1].weight,
-                                                      fl[0].block[1].bias, fl[0].block[1].running_mean,
-                                                      fl[0].block[1].running_var, fl[0].block[1].eps, device=dev),
-                      torch.bfloat16)
-    h = h.permute(0, 2, 3, 4, 1).contiguous()
-    for i in (1, 2, 3):
-        h = v2v.res3d_block(h, v2v.fold_res3d_block(fl[i], device=dev))
-    s1 = v2v.res3d_block(h, v2v.fold_res3d_block(ed.skip_res1, device=dev))
-    x = v2v.v2v_interior(ev.interior, h.permute(0, 4, 1, 2, 3).float())
-    x = (x + s1.permute(0, 4, 1, 2, 3)).permute(0, 2, 3, 4, 1).to(torch.bfloat16).contiguous()
-    return v2v.res3d_block(x, v2v.fold_res3d_block(m.back_layers[0], device=dev))
-
-
 @pytest.mark.gpu
 def test_v2veval_wiring(device):
     """trunk and forward equal, bit for bit, the same chain written out here (V = 32, B = 2); the
@@ -776,35 +415,9 @@ def test_v2veval_wiring(device):
     assert_same_bits(out, out_w)
 
 
-def bf16_operand_model(m):
-    """The stand-in on the CPU with every conv operand rounded to bf16: weights rounded once, the
-    input of every Conv3d / ConvTranspose3d rounded by a forward pre-hook; everything else f32."""
-    import copy
-    mb = copy.deepcopy(m)
-    with torch.no_grad():
-        for mod in mb.modules():
-            if isinstance(mod, (nn.Conv3d, nn.ConvTranspose3d)):
-                mod.weight.copy_(bf16r(mod.weight))
-                mod.register_forward_pre_hook(lambda _m, args: (bf16r(args[0]),))
-    return mb
-
-
-E2E_SIDE = 2500.0
-E2E_MULT = 10.0
 # measured on the MI355X (see test_v2veval_against_the_f32_modules): the bars are twice these
 E2E_TRUNK_MEASURED = 6.630e-3
 E2E_JOINTS_MEASURED = 5.979e-3
-
-
-def e2e_case(device):
-    """Blob-like input (synth.blob_volumes in the first 17 of 32 channels, unit noise elsewhere)
-    and a multiplier that makes the stand-in's logits peaked."""
-    from mvn_rocm import synth, volumetric
-    V = 32
-    coords = volumetric.build_coord_volumes(np.array([[10.0, -20.0, 900.0]]), E2E_SIDE, V, theta=[0.3], device=device)
-    blobs = synth.blob_volumes(coords, J, seed=4).cpu()
-    x = torch.cat([blobs, 0.1 * torch.randn(1, 32 - J, V, V, V, generator=torch.Generator().manual_seed(2))], dim=1)
-    return bf16r(x), coords
 
 
 def e2e_measure(device, mult=None):

@@ -9,7 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from test_feature_conv_api import stand_in_net
-from test_gpu_v2v_res3d import E2E_MULT, assert_same_bits
+from v2v_kit import E2E_MULT, assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +20,7 @@ def blob_features(vb, seed):
     """Backbone-like maps: per frame J points inside the cuboid; channel c of every view holds a 2D
     Gaussian (height 5, sigma 1.5 pixels) at the projection of point c mod J, over 0.1 x unit noise.
     Any 1x1 convolution of them is a mixture of the same J blobs, their unprojection J blobs in the
-    volume (largest voxel 10.7 here, as the blobs of height 10 of test_gpu_v2v_res3d.e2e_case), which
+    volume (largest voxel 10.7 here, as the blobs of height 10 of v2v_kit.e2e_case), which
     keeps the soft-argmax well conditioned under that test's multiplier: every joint's largest logit
     is 13 or more above its mean on the CPU reference."""
     g = torch.Generator().manual_seed(seed)

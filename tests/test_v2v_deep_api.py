@@ -5,7 +5,8 @@ import pytest
 import torch
 from torch import nn
 
-from test_gpu_v2v_res3d import Basic3DBlock, Res3DBlock, Upsample3DBlock, V2VModel, randomise
+from v2v_kit import (Basic3DBlock, Res3DBlock, Upsample3DBlock, V2VModel, bn_fold64, randomise, unpack_conv3, unpack_skip,
+                     unpack_upsample, vol)
 
 ARG, SHAPE = -1, -2
 NONE, IDENTITY, POINTWISE = 0, 1, 2
@@ -96,43 +97,19 @@ def test_upsample2_deep_argument_validation(lib):
 def unpack_deep(packed, cin):
     """The (128, cin, 3, 3, 3) weight from the documented layout of mvn_v2v_conv3_deep (mvn_hip.h):
     [tap][kp][m][lane][j] = W[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]."""
-    W = torch.full((128, cin, 27), float("nan"), dtype=torch.float64)
-    p = packed.cpu().double()
-    assert tuple(p.shape) == (27, cin // 32, 8, 64, 8)
-    for kp in range(cin // 32):
-        for m in range(8):
-            for lane in range(64):
-                for j in range(8):
-                    W[16 * m + (lane & 15), 32 * kp + 8 * (lane >> 4) + j] = p[:, kp, m, lane, j]
-    return W.view(128, cin, 3, 3, 3)
+    return unpack_conv3(packed, 128, cin)
 
 
 def unpack_deep_skip(packed):
-    W = torch.full((128, 64), float("nan"), dtype=torch.float64)
-    p = packed.cpu().double()
-    assert tuple(p.shape) == (2, 8, 64, 8)
-    for kp in range(2):
-        for m in range(8):
-            for lane in range(64):
-                for j in range(8):
-                    W[16 * m + (lane & 15), 32 * kp + 8 * (lane >> 4) + j] = p[kp, m, lane, j]
-    return W
+    assert tuple(packed.shape) == (2, 8, 64, 8)
+    return unpack_skip(packed, 128, 64)
 
 
 def unpack_upsample_deep(packed, cout):
     """The (128, cout, 2, 2, 2) ConvTranspose3d weight from mvn_v2v_upsample2_deep's documented
     layout, H = cout / 16: [kp][m][lane][j] = W[32 kp + 8 (lane >> 4) + j][16 (m % H) + (lane & 15)]
     [dx][dy][dz], (dx*2 + dy)*2 + dz = m // H."""
-    H = cout // 16
-    W = torch.full((128, cout, 8), float("nan"), dtype=torch.float64)
-    p = packed.cpu().double()
-    assert tuple(p.shape) == (4, 8 * H, 64, 8)
-    for kp in range(4):
-        for m in range(8 * H):
-            for lane in range(64):
-                for j in range(8):
-                    W[32 * kp + 8 * (lane >> 4) + j, 16 * (m % H) + (lane & 15), m // H] = p[kp, m, lane, j]
-    return W.view(128, cout, 2, 2, 2)
+    return unpack_upsample(packed, 128, cout)
 
 
 @pytest.mark.parametrize("cin", (64, 128))
@@ -146,12 +123,6 @@ def test_pack_functions_against_an_independent_unpack(cin):
     assert torch.equal(unpack_deep_skip(v2v.pack_pointwise_skip_deep_weight(ws)), ws)
     wu = torch.randn(128, cin, 2, 2, 2, generator=g).bfloat16().double()        # cout = cin: 64 | 128
     assert torch.equal(unpack_upsample_deep(v2v.pack_upsample_deep_weight(wu), cin), wu)
-
-
-def bn_fold64(conv, bn):
-    s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-    b = conv.bias.double() if conv.bias is not None else torch.zeros_like(s)
-    return s, (b - bn.running_mean.double()) * s + bn.bias.double()
 
 
 @pytest.mark.parametrize("bias", (True, False), ids=("bias", "no_bias"))
@@ -232,10 +203,6 @@ def test_folds_refuse_other_modules():
 
 
 # ---------------------------------------------------------------- the Python layer's refusals
-def vol(B, D, C, dtype=torch.bfloat16):
-    return torch.zeros(B, D, D, D, C, dtype=dtype)
-
-
 def test_conv3_deep_refusals():
     from mvn_rocm import v2v
     p = v2v.fold_res3d_block_deep(randomise(Res3DBlock(64, 128), 2), device="cpu")

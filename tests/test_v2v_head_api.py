@@ -5,7 +5,8 @@ import torch
 from torch import nn
 from torch.fx.experimental.proxy_tensor import make_fx
 
-from test_gpu_v2v_head import Basic3DBlock, C, bf16r, make_head, restate, unpack, exceed, CAP, LOOSE
+from test_gpu_v2v_head import C, bf16r, make_head, restate, unpack, exceed, CAP, LOOSE
+from v2v_kit import Basic3DBlock
 
 
 @pytest.fixture(scope="module")

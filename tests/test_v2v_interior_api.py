@@ -5,7 +5,8 @@ import pytest
 import torch
 from torch import nn
 
-from test_gpu_v2v_res3d import EncoderDecorder, Res3DBlock, Upsample3DBlock, V2VModel, randomise
+from v2v_kit import (EncoderDecorder, Res3DBlock, Upsample3DBlock, V2VModel, bn_fold64, randomise, unpack_conv3,
+                     unpack_skip, unpack_upsample as unpack_up, vol)
 
 ARG, SHAPE = -1, -2
 NONE, IDENTITY, POINTWISE = 0, 1, 2
@@ -91,47 +92,18 @@ def test_upsample_and_pool_argument_validation(lib):
 def unpack_wide(packed, cin):
     """The (64, cin, 3, 3, 3) weight from the documented layout of mvn_v2v_conv3_wide (mvn_hip.h):
     [tap][kp][m][lane][j] = W[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][dx][dy][dz]."""
-    W = torch.zeros(64, cin, 27, dtype=torch.float64)
-    p = packed.cpu().double()
-    assert tuple(p.shape) == (27, cin // 32, 4, 64, 8)
-    for kp in range(cin // 32):
-        for m in range(4):
-            for lane in range(64):
-                for j in range(8):
-                    W[16 * m + (lane & 15), 32 * kp + 8 * (lane >> 4) + j] = p[:, kp, m, lane, j]
-    return W.view(64, cin, 3, 3, 3)
+    return unpack_conv3(packed, 64, cin)
 
 
 def unpack_wide_skip(packed):
-    W = torch.zeros(64, 32, dtype=torch.float64)
-    p = packed.cpu().double()
-    assert tuple(p.shape) == (4, 64, 8)
-    for m in range(4):
-        for lane in range(64):
-            for j in range(8):
-                W[16 * m + (lane & 15), 8 * (lane >> 4) + j] = p[m, lane, j]
-    return W
+    return unpack_skip(packed, 64, 32)
 
 
 def unpack_upsample(packed):
     """The (64, 32, 2, 2, 2) ConvTranspose3d weight from mvn_v2v_upsample2's documented layout:
     [kp][m][lane][j] = W[32 kp + 8 (lane >> 4) + j][16 (m & 1) + (lane & 15)][dx][dy][dz],
     (dx*2 + dy)*2 + dz = m >> 1."""
-    W = torch.zeros(64, 32, 8, dtype=torch.float64)
-    p = packed.cpu().double()
-    assert tuple(p.shape) == (2, 16, 64, 8)
-    for kp in range(2):
-        for m in range(16):
-            for lane in range(64):
-                for j in range(8):
-                    W[32 * kp + 8 * (lane >> 4) + j, 16 * (m & 1) + (lane & 15), m >> 1] = p[kp, m, lane, j]
-    return W.view(64, 32, 2, 2, 2)
-
-
-def bn_fold64(conv, bn):
-    s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-    b = conv.bias.double() if conv.bias is not None else torch.zeros_like(s)
-    return s, (b - bn.running_mean.double()) * s + bn.bias.double()
+    return unpack_up(packed, 64, 32)
 
 
 @pytest.mark.parametrize("cin", (32, 64))
@@ -215,10 +187,6 @@ def test_folds_refuse_other_modules():
 
 
 # ---------------------------------------------------------------- the Python layer's refusals
-def vol(B, V, C, dtype=torch.bfloat16):
-    return torch.zeros(B, V, V, V, C, dtype=dtype)
-
-
 def test_max_pool2_cl_refusals():
     from mvn_rocm import v2v
     with pytest.raises(TypeError, match="bfloat16"):

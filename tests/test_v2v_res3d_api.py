@@ -6,10 +6,11 @@ import torch.nn.functional as F
 from torch import nn
 from torch.fx.experimental.proxy_tensor import make_fx
 
-from test_gpu_v2v_res3d import CO, Res3DBlock, V2VModel, randomise
+from v2v_kit import IDENTITY, NONE, POINTWISE, Res3DBlock, V2VModel, randomise, unpack_conv3, unpack_skip as unpack_skip_w
+from v2v_kit import bn_fold64 as fold64
 
+CO = 32
 ARG, SHAPE, WORKSPACE = -1, -2, -5
-NONE, IDENTITY, POINTWISE = 0, 1, 2
 
 
 @pytest.fixture(scope="module")
@@ -104,33 +105,15 @@ def test_res3d_argument_validation(lib):
 def unpack3(packed):
     """The (32, 32, 3, 3, 3) weight from the documented layout of mvn_v2v_conv3 (mvn_hip.h):
     [tap = (dx*3 + dy)*3 + dz][m][lane][j] = W[16 m + (lane & 15)][8 (lane >> 4) + j][dx][dy][dz]."""
-    W = torch.zeros(CO, 32, 27, dtype=torch.float64)
-    p = packed.cpu().double()
-    for m in range(2):
-        for lane in range(64):
-            for j in range(8):
-                W[16 * m + (lane & 15), 8 * (lane >> 4) + j] = p[:, m, lane, j]
-    return W.view(CO, 32, 3, 3, 3)
+    return unpack_conv3(packed, CO)
 
 
 def unpack_skip(packed):
-    W = torch.zeros(CO, 32, dtype=torch.float64)
-    p = packed.cpu().double()
-    for m in range(2):
-        for lane in range(64):
-            for j in range(8):
-                W[16 * m + (lane & 15), 8 * (lane >> 4) + j] = p[m, lane, j]
-    return W
+    return unpack_skip_w(packed, CO)
 
 
 def bf16r(t):
     return t.float().to(torch.bfloat16).double()
-
-
-def fold64(conv, bn):
-    s = bn.weight.detach().double() / torch.sqrt(bn.running_var.double() + bn.eps)
-    b = conv.bias.detach().double() if conv.bias is not None else torch.zeros(CO, dtype=torch.float64)
-    return s, (b - bn.running_mean.double()) * s + bn.bias.detach().double()
 
 
 @pytest.mark.parametrize("cin,bias", ((16, True), (32, True), (32, False), (16, False)))
