@@ -43,6 +43,8 @@
  *                           normalisation, the upscale and mvn_dlt in one launch)
  *   mvn_feature_conv       <- mvn/models/triangulation.py:238-240, :345 process_features,
  *                           Conv2d(256, 32, 1)
+ *   mvn_deconv4s2          <- mvn/models/pose_resnet.py:266-291 (one ConvTranspose2d(k = 4, stride 2)
+ *                           + BatchNorm2d + ReLU of the backbone's deconv head; eval mode)
  *
  * Conventions
  *   - Every buffer is caller-owned device memory (hipMalloc / torch), contiguous,
@@ -538,6 +540,52 @@ int mvn_v2v_upsample2_deep(const void* x, int cout, const void* weight_packed, c
  */
 int mvn_feature_conv(const void* x, int x_dtype, const float* weight, const float* bias, void* out,
                      int out_dtype, int64_t n_images, int cin, int cout, int H, int W, void* stream);
+
+/*
+ * One layer of the 2-D backbone's deconv head (mvn/models/pose_resnet.py:266-291), eval mode:
+ * ConvTranspose2d(cin, 256, k = 4, stride 2, padding 1, output_padding 0, bias folded) +
+ * BatchNorm2d + ReLU on v_mfma_f32_16x16x32_bf16.  Per image n, output pixel
+ * (oy, ox) of the 2H x 2W map and output channel co:
+ *   acc = sum of x[n, iy, ix, ci] * W[ci][co][ky][kx] over ci and the (ky, kx) with
+ *         oy = 2 iy - 1 + ky, ox = 2 ix - 1 + kx, 0 <= iy < H, 0 <= ix < W
+ *         (products of bf16 operands, accumulated in f32 on the MFMA, summation order free)
+ *   r   = fmaf(acc, scale[co], shift[co])
+ *   y   = r <= 0 ? +0 : r                                          (a NaN stays NaN)
+ *   out = y rounded once to out_dtype (bf16: nearest-even)
+ * An even oy takes ky in {1, 3} (iy = oy / 2, oy / 2 - 1), an odd oy takes ky in {0, 2}
+ * (iy = (oy + 1) / 2, (oy - 1) / 2), and the same along x: 2 x 2 taps in the interior, fewer on the
+ * border, where a tap outside the image contributes zero and never reads the neighbouring image.
+ *   x              (n_images, H, W, cin) bf16, channels-last
+ *   cin            a multiple of 32 in [32, 2048]
+ *   weight_packed  mvn_deconv4s2_packed_weight_bytes(cin) = 16 * (cin / 32) * 16 * 64 * 8 * 2 bytes:
+ *                  bf16 as [tap = ky*4 + kx][kp 0..cin/32-1][m 0..15][lane 0..63][j 0..7]
+ *                    = W[32 kp + 8 (lane >> 4) + j][16 m + (lane & 15)][ky][kx]
+ *                  (W the ConvTranspose2d weight (cin, 256, 4, 4), rounded to bf16)
+ *   scale, shift   (256) f32: BN and the deconv bias (if any) folded
+ *   out_layout     MVN_LAYOUT_NHWC: out (n_images, 2H, 2W, 256), bf16 only (feeds the next layer);
+ *                  MVN_LAYOUT_NCHW: out (n_images, 256, 2H, 2W), bf16 or f32
+ *   H, W           >= 1, with H * W <= (2^31 - 1) / (2 cin) and <= (2^31 - 1) / 4096: one image of x
+ *                  and one image of out (256 * 2H * 2W elements of up to 4 bytes) each stay below
+ *                  2^31 bytes, the range of one buffer resource; the batch may be larger
+ * x, weight_packed, scale, shift and out are 16-byte aligned.  The three outputs agree: the
+ * channels-last result equals the NCHW bf16 result after a permute, and the NCHW f32 result
+ * rounded to bf16 equals the NCHW bf16 result, bit for bit (the same MFMA sums in the same order,
+ * one rounding).  Where W % 4 == 0 an NCHW lane stores 8 consecutive outputs of a row as 16-byte
+ * words, elsewhere single elements, with the same bits.  Deterministic (no atomics).  A NaN or
+ * infinite input pixel (iy, ix) reaches exactly the output rows 2 iy - 1 .. 2 iy + 2 and columns
+ * 2 ix - 1 .. 2 ix + 2 of its own image, clipped, in all 256 channels.  No load touches a byte
+ * outside x (range-checked buffer resource per image) and no store a byte outside out.
+ * Checked before any HIP call, all MVN_ERR_ARG: a null pointer, an unknown layout or dtype (f32
+ * with NHWC included), a cin outside the set, n_images < 0, H < 1 or W < 1, an image over the
+ * limits above, more than INT_MAX blocks (n_images * ceil(H / 4) * ceil(W / 16) * 2), a pointer off
+ * its alignment.  n_images == 0 returns MVN_OK without a launch.  The size function returns 0 for
+ * a cin outside the set.  Stream-ordered, allocates nothing, reentrant.
+ */
+#define MVN_LAYOUT_NCHW 0      /* (M, C, H, W)                                      */
+#define MVN_LAYOUT_NHWC 1      /* (M, H, W, C): channels-last                       */
+size_t mvn_deconv4s2_packed_weight_bytes(int cin);
+int mvn_deconv4s2(const void* x, const void* weight_packed, const float* scale, const float* shift, void* out,
+                  int out_layout, int out_dtype, int64_t n_images, int cin, int H, int W, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

@@ -20,6 +20,7 @@ MVN_DTYPE_F32 = 0
 MVN_DTYPE_BF16 = 1
 MVN_AGG_SUM, MVN_AGG_MAX, MVN_AGG_SOFTMAX, MVN_AGG_CONF = 0, 1, 2, 3
 MVN_LAYOUT_NCDHW, MVN_LAYOUT_NDHWC = 0, 1
+MVN_LAYOUT_NCHW, MVN_LAYOUT_NHWC = 0, 1
 MVN_PRECISION_EXACT, MVN_PRECISION_FAST = 0, 1
 MVN_SKIP_NONE, MVN_SKIP_IDENTITY, MVN_SKIP_POINTWISE = 0, 1, 2
 
@@ -88,6 +89,8 @@ SIGNATURES = {
     "mvn_v2v_upsample2_deep": (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 5 + [_c_int, _c_int, _c_void_p]),
     "mvn_feature_conv": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_i64]
                          + [_c_int] * 4 + [_c_void_p]),
+    "mvn_deconv4s2_packed_weight_bytes": (_c_size_t, [_c_int]),
+    "mvn_deconv4s2": (_c_int, [_c_void_p] * 5 + [_c_int, _c_int, _c_i64, _c_int, _c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
                                         _c_void_p, _c_void_p] + [_c_int] * 8 + [_c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward_workspace_bytes": (_c_size_t, [_c_int] * 5),

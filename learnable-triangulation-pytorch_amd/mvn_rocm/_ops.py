@@ -429,6 +429,36 @@ def _(x, weight, bias, out_dtype):
     return x.new_empty((M, FEATURE_COUT, H, W), dtype=_CODE_DTYPE[out_dtype])
 
 
+# --------------------------------------------------------------------------- backbone deconv head
+DECONV_COUT = 256             # csrc/deconv_head.hip: every layer of the head has 256 output channels
+
+
+def _deconv_out_shape(x: Tensor, nchw: bool):
+    M, H, W, _ = x.shape
+    return (M, DECONV_COUT, 2 * H, 2 * W) if nchw else (M, 2 * H, 2 * W, DECONV_COUT)
+
+
+@_op("deconv4s2")
+def deconv4s2(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, nchw: bool, out_dtype: int) -> Tensor:
+    """x (M,H,W,Cin) bf16 channels-last -> relu(bn(conv_transpose2d_4s2(x))) as (M,2H,2W,256) bf16
+    (nchw False) or (M,256,2H,2W) of dtype code `out_dtype` (nchw True) (csrc/deconv_head.hip)."""
+    _require_gpu(x, packed, scale, shift)
+    M, H, W, cin = x.shape
+    out = torch.empty(_deconv_out_shape(x, nchw), dtype=_CODE_DTYPE[out_dtype], device=x.device)
+    if M == 0:                            # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_deconv4s2(x.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                     out.data_ptr(), _lib.MVN_LAYOUT_NCHW if nchw else _lib.MVN_LAYOUT_NHWC,
+                                     out_dtype, M, cin, H, W, _stream(x))
+    _lib.check(code, "mvn_deconv4s2")
+    return out
+
+
+@deconv4s2.register_fake
+def _(x, packed, scale, shift, nchw, out_dtype):
+    return x.new_empty(_deconv_out_shape(x, nchw), dtype=_CODE_DTYPE[out_dtype])
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,
