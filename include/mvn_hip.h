@@ -45,6 +45,8 @@
  *                           Conv2d(256, 32, 1)
  *   mvn_deconv4s2          <- mvn/models/pose_resnet.py:266-291 (one ConvTranspose2d(k = 4, stride 2)
  *                           + BatchNorm2d + ReLU of the backbone's deconv head; eval mode)
+ *   mvn_deconv4s2_project  <- the head's last layer (as mvn_deconv4s2) and process_features,
+ *                           mvn/models/triangulation.py:238-240, :345, in one launch
  *
  * Conventions
  *   - Every buffer is caller-owned device memory (hipMalloc / torch), contiguous,
@@ -586,6 +588,44 @@ int mvn_feature_conv(const void* x, int x_dtype, const float* weight, const floa
 size_t mvn_deconv4s2_packed_weight_bytes(int cin);
 int mvn_deconv4s2(const void* x, const void* weight_packed, const float* scale, const float* shift, void* out,
                   int out_layout, int out_dtype, int64_t n_images, int cin, int H, int W, void* stream);
+
+/*
+ * The head's last layer with the volumetric model's process_features (or any Conv2d(256, 32, 1))
+ * behind it in the same launch: mvn_deconv4s2 followed by a 256 -> 32 product
+ * per output pixel, the 256-channel activation never stored to global memory.  x, weight_packed,
+ * scale, shift, cin, H, W as for mvn_deconv4s2.  Per image n and output pixel (oy, ox):
+ *   a[c]   = bf16(relu_keep_nan(fmaf(acc[c], scale[c], shift[c])))     c = 0 .. 255
+ *            acc the same MFMA sums in the same order as mvn_deconv4s2's, so a is bit for bit what
+ *            mvn_deconv4s2 writes with MVN_LAYOUT_NCHW / MVN_DTYPE_BF16
+ *   out[p] = bias[p] + sum_c a[c] * hi[p][c] + sum_c a[c] * lo[p][c]   p = 0 .. 31
+ *            hi = bf16(w), lo = bf16(w - hi) for the f32 projection weight w (32, 256), split once
+ *            by the packer: hi + lo is within 2^-17 relative of w.  Products of bf16 operands
+ *            (exact), accumulated in f32 on v_mfma_f32_16x16x32_bf16 in one fixed order: the
+ *            accumulator starts at bias[p] and takes, for the 32-channel groups k = 0 .. 7 in
+ *            ascending order, the MFMA of group k with hi and then the MFMA of group k with lo.
+ *            No atomics: the same inputs give the same bits on every run and for every n_images.
+ *   out    = that f32 value, or it rounded once to bf16 (nearest-even)
+ *   proj_packed  mvn_deconv4s2_project_weight_bytes() = 2 * 8 * 2 * 64 * 8 * 2 = 32,768 bytes: bf16 as
+ *                [part 0 = hi | 1 = lo][k 0..7][nt 0..1][lane 0..63][j 0..7]
+ *                  = part(w[16 nt + (lane & 15)][32 k + 16 (j >> 2) + 4 (lane >> 4) + (j & 3)])
+ *                (the K-slots of a group in the order in which a lane of the deconv's MFMA holds the
+ *                channels of a pixel).  A projection with fewer than 32 rows is zero-padded.
+ *   bias         (32) f32
+ *   out          (n_images, 32, 2H, 2W) NCHW, out_dtype f32 or bf16
+ * Where any a[c] of a pixel is NaN or infinite, that pixel's 32 outputs may each be NaN or
+ * infinite, which one unspecified (inf * lo with lo = 0 is NaN); no other pixel is affected.  An
+ * input pixel reaches the same clipped 4 x 4 box of outputs as in mvn_deconv4s2.  No load touches
+ * a byte outside x and no store a byte outside out; where W % 4 == 0 a lane stores 8 consecutive
+ * outputs of a row as 16-byte words, elsewhere single elements, with the same bits.
+ * Checked before any HIP call, all MVN_ERR_ARG: a null pointer (bias included), an unknown dtype,
+ * a cin outside the set, n_images < 0, H < 1 or W < 1, an image over mvn_deconv4s2's limits, more
+ * than INT_MAX / 2 blocks (n_images * ceil(H / 4) * ceil(W / 16)), a pointer off 16-byte alignment.
+ * n_images == 0 returns MVN_OK without a launch.  Stream-ordered, allocates nothing, reentrant.
+ */
+size_t mvn_deconv4s2_project_weight_bytes(void);
+int mvn_deconv4s2_project(const void* x, const void* weight_packed, const float* scale, const float* shift,
+                          const void* proj_packed, const float* bias, void* out, int out_dtype, int64_t n_images,
+                          int cin, int H, int W, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

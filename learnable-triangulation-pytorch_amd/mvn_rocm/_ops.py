@@ -459,6 +459,30 @@ def _(x, packed, scale, shift, nchw, out_dtype):
     return x.new_empty(_deconv_out_shape(x, nchw), dtype=_CODE_DTYPE[out_dtype])
 
 
+@_op("deconv4s2_project")
+def deconv4s2_project(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, proj: Tensor, bias: Tensor,
+                      out_dtype: int) -> Tensor:
+    """x (M,H,W,Cin) bf16 channels-last -> the 256 -> 32 projection (proj packed hi | lo, bias (32,) f32) of
+    relu(bn(conv_transpose2d_4s2(x))) rounded to bf16, as (M,32,2H,2W) of dtype code `out_dtype`; the
+    256-channel map is not stored (csrc/deconv_head.hip)."""
+    _require_gpu(x, packed, scale, shift, proj, bias)
+    M, H, W, cin = x.shape
+    out = torch.empty((M, FEATURE_COUT, 2 * H, 2 * W), dtype=_CODE_DTYPE[out_dtype], device=x.device)
+    if M == 0:                            # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_deconv4s2_project(x.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                             proj.data_ptr(), bias.data_ptr(), out.data_ptr(), out_dtype, M, cin, H, W,
+                                             _stream(x))
+    _lib.check(code, "mvn_deconv4s2_project")
+    return out
+
+
+@deconv4s2_project.register_fake
+def _(x, packed, scale, shift, proj, bias, out_dtype):
+    M, H, W, _ = x.shape
+    return x.new_empty((M, FEATURE_COUT, 2 * H, 2 * W), dtype=_CODE_DTYPE[out_dtype])
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,

@@ -2,6 +2,8 @@
 DESIGN.md §4.16): the three ``ConvTranspose2d(Cin, 256, 4, stride=2, padding=1)`` + ``BatchNorm2d``
 + ``ReLU`` that take ``layer4``'s maps to the 256-channel feature maps, one ``deconv4s2`` launch
 each (csrc/deconv_head.hip, bf16 MFMA), and ``final_layer`` through ``model.feature_conv``.
+``deconv4s2_project`` is the last layer with the volumetric model's ``process_features`` behind it
+in the same launch: the 256-channel maps are not written.
 
 ``DeconvHeadEval`` is the head alone, from ``layer4``'s output to ``(heatmaps, features)``;
 ``BackboneEval`` is the reference's ``PoseResNet.forward`` with its own trunk modules in front of
@@ -15,7 +17,7 @@ import torch
 from torch import nn
 
 from . import _ops
-from .model import feature_conv
+from .model import _feature_conv_params, feature_conv
 from .op import _dtype_code
 from .v2v import _bn_fold, _f64, _inference_only, _pack_mfma_a
 
@@ -87,6 +89,22 @@ def _aligned(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+def _check_deconv_call(what, x_cl, p):
+    """The input and parameter checks that ``deconv4s2`` and ``deconv4s2_project`` share."""
+    if x_cl.dtype != torch.bfloat16:
+        raise TypeError(f"{what}: x_cl must be bfloat16, got {x_cl.dtype}")
+    if x_cl.dim() != 4:
+        raise RuntimeError(f"{what}: x_cl must be (M, H, W, Cin), got {tuple(x_cl.shape)}")
+    M, H, W, cin = x_cl.shape
+    _check_cin(what, cin)
+    if H < 1 or W < 1 or H * W > min(MAX_PIXELS, (2 ** 31 - 1) // (2 * cin)):
+        raise RuntimeError(f"{what}: H and W must be at least 1 with one image below 2^31 bytes on both sides, got {H} x {W}")
+    shape = (16, cin // 32, COUT // 16, 64, 8)
+    if (tuple(p.packed.shape) != shape or p.packed.dtype != torch.bfloat16 or tuple(p.scale.shape) != (COUT,)
+            or tuple(p.shift.shape) != (COUT,) or p.scale.dtype != torch.float32 or p.shift.dtype != torch.float32):
+        raise RuntimeError(f"{what}: packed weights {shape}, scale and shift ({COUT},) must be what fold_deconv_block returns")
+
+
 def deconv4s2(x_cl, params, out_layout="cl", out_dtype=None):
     """One launch of mvn_deconv4s2: x_cl (M, H, W, Cin) bfloat16 channels-last ->
     ``relu(bn(conv_transpose2d(x, w, stride=2, padding=1)))`` with ``params`` from ``fold_deconv_block``, as
@@ -103,20 +121,61 @@ def deconv4s2(x_cl, params, out_layout="cl", out_dtype=None):
     od = _dtype_code(out_dtype)
     if out_layout == "cl" and out_dtype != torch.bfloat16:
         raise TypeError(f"{what}: the channels-last output is bfloat16, got {out_dtype}")
-    if x_cl.dtype != torch.bfloat16:
-        raise TypeError(f"{what}: x_cl must be bfloat16, got {x_cl.dtype}")
-    if x_cl.dim() != 4:
-        raise RuntimeError(f"{what}: x_cl must be (M, H, W, Cin), got {tuple(x_cl.shape)}")
-    M, H, W, cin = x_cl.shape
-    _check_cin(what, cin)
-    if H < 1 or W < 1 or H * W > min(MAX_PIXELS, (2 ** 31 - 1) // (2 * cin)):
-        raise RuntimeError(f"{what}: H and W must be at least 1 with one image below 2^31 bytes on both sides, got {H} x {W}")
-    shape = (16, cin // 32, COUT // 16, 64, 8)
-    if (tuple(p.packed.shape) != shape or p.packed.dtype != torch.bfloat16 or tuple(p.scale.shape) != (COUT,)
-            or tuple(p.shift.shape) != (COUT,) or p.scale.dtype != torch.float32 or p.shift.dtype != torch.float32):
-        raise RuntimeError(f"{what}: packed weights {shape}, scale and shift ({COUT},) must be what fold_deconv_block returns")
+    _check_deconv_call(what, x_cl, p)
     return _ops.call(_ops.deconv4s2, _aligned(x_cl), _aligned(p.packed), _aligned(p.scale), _aligned(p.shift),
                      out_layout == "nchw", od)
+
+
+class ProjectionParams(NamedTuple):
+    """What ``pack_projection`` returns: the packed bf16 hi | lo weight and the f32 bias."""
+    packed: torch.Tensor
+    bias: torch.Tensor
+
+
+PROJ_SHAPE = (2, COUT // 32, FINAL_ROWS // 16, 64, 8)
+
+
+def pack_projection(weight, bias=None, device="cuda"):
+    """A ``Conv2d(256, 32, 1)`` weight, (32, 256) or (32, 256, 1, 1), and bias ((32,), None for zeros) ->
+    ``ProjectionParams`` on ``device`` as mvn_deconv4s2_project reads them.  The float32 weight is split
+    in float64 into two bfloat16 parts, ``hi = bf16(w)`` and ``lo = bf16(w - hi)`` (hi + lo is within
+    2^-17 relative of w), packed (2, 8, 2, 64, 8):
+    [part hi | lo][k][nt][lane][j] = part(w[16 nt + (lane & 15)][32 k + 16 (j >> 2) + 4 (lane >> 4) + (j & 3)])."""
+    if tuple(weight.shape) not in ((FINAL_ROWS, COUT), (FINAL_ROWS, COUT, 1, 1)):
+        raise RuntimeError(f"pack_projection: weight must be ({FINAL_ROWS}, {COUT}) or ({FINAL_ROWS}, {COUT}, 1, 1), got "
+                           f"{tuple(weight.shape)}")
+    if bias is not None and tuple(bias.shape) != (FINAL_ROWS,):
+        raise RuntimeError(f"pack_projection: bias must be ({FINAL_ROWS},), got {tuple(bias.shape)}")
+    w = _f64(weight.detach().float()).reshape(FINAL_ROWS, COUT)
+    hi = w.float().bfloat16()
+    lo = (w - hi.double()).float().bfloat16()                    # the difference is exact in float64 and in float32
+    parts = torch.stack((hi, lo)).reshape(2, FINAL_ROWS // 16, 16, COUT // 32, 2, 4, 4)   # [part][nt][n][k][j >> 2][g][j & 3]
+    packed = parts.permute(0, 3, 1, 5, 2, 4, 6).reshape(PROJ_SHAPE).contiguous()          # [part][k][nt][g][n][j]
+    dev = torch.device(device)
+    b = torch.zeros(FINAL_ROWS) if bias is None else bias.detach().float().cpu().clone()
+    return ProjectionParams(packed.to(dev), b.to(dev))
+
+
+def deconv4s2_project(x_cl, params, proj, out_dtype=None):
+    """One launch of mvn_deconv4s2_project: ``deconv4s2(x_cl, params, "nchw", bfloat16)`` followed by the
+    256 -> 32 1x1 convolution of ``proj`` (``pack_projection``), without the 256-channel maps in between:
+    x_cl (M, H, W, Cin) bfloat16 channels-last -> (M, 32, 2H, 2W) bfloat16 | float32 (``out_dtype``, default
+    bfloat16).  The activation is what ``deconv4s2`` rounds to bfloat16, bit for bit; the projection is
+    ``bias + sum a hi + sum a lo`` in f32 on the MFMA in one fixed order, rounded once for a bfloat16
+    output.  The checks and errors of ``deconv4s2``.  GPU only; inference-only."""
+    what = "deconv4s2_project"
+    p, pr = DeconvParams(*params), ProjectionParams(*proj)
+    _inference_only(what, x_cl, *p, *pr, instead="the backbone's own deconv_layers and the model's process_features, "
+                    "which autograd records")
+    out_dtype = torch.bfloat16 if out_dtype is None else out_dtype
+    od = _dtype_code(out_dtype)
+    _check_deconv_call(what, x_cl, p)
+    if (tuple(pr.packed.shape) != PROJ_SHAPE or pr.packed.dtype != torch.bfloat16 or tuple(pr.bias.shape) != (FINAL_ROWS,)
+            or pr.bias.dtype != torch.float32):
+        raise RuntimeError(f"{what}: the packed projection {PROJ_SHAPE} and bias ({FINAL_ROWS},) must be what "
+                           "pack_projection returns")
+    return _ops.call(_ops.deconv4s2_project, _aligned(x_cl), _aligned(p.packed), _aligned(p.scale), _aligned(p.shift),
+                     _aligned(pr.packed), _aligned(pr.bias), od)
 
 
 def _final_layer_params(final_layer):
@@ -164,6 +223,13 @@ def _deconv_triples(deconv_layers):
     return triples
 
 
+def _no_heatmaps_with_project(heatmaps):
+    if heatmaps:
+        raise RuntimeError("DeconvHeadEval: project and heatmaps=True exclude each other: with the projection in the "
+                           "last layer's launch the 256-channel map is not formed, so final_layer has nothing to read; "
+                           "pass heatmaps=False, or keep the unfused head")
+
+
 class DeconvHeadEval(nn.Module):
     """``deconv_layers`` and ``final_layer`` of the reference's ``PoseResNet`` (pose_resnet.py:312-316),
     eval mode: ``module(x)`` takes ``layer4``'s output (M, Cin, h, w), float32 or bfloat16 in any memory
@@ -177,12 +243,20 @@ class DeconvHeadEval(nn.Module):
     3. ``heatmaps``: ``model.feature_conv`` with ``final_layer``'s weight and bias zero-padded to 32 rows,
        sliced to the J joints and made contiguous (``heatmaps=False``: skipped, None returned).
 
+    With ``project`` (a ``ProjectionParams``; ``from_reference(..., process_features=)`` packs the
+    volumetric model's), the last layer runs ``deconv4s2_project`` and the module returns ``(None,
+    features32 (M, 32, 8h, 8w) in feature_dtype)``: what ``model.feature_conv`` makes of the 256-channel
+    maps, which are not formed.  ``heatmaps`` must then be False.
+
     Every layer runs on the kernel: none of them is slower there than in torch.  The
     parameters are copied: later changes to the backbone do not reach this module."""
 
-    def __init__(self, params, final_weight, final_bias, joints, feature_dtype=torch.bfloat16, heatmaps=True):
+    def __init__(self, params, final_weight, final_bias, joints, feature_dtype=torch.bfloat16, heatmaps=True,
+                 project=None):
         super().__init__()
         _dtype_code(feature_dtype)
+        if project is not None:
+            _no_heatmaps_with_project(heatmaps)
         self.n_layers = len(params)
         for i, p in enumerate(params):
             p = DeconvParams(*p)
@@ -194,18 +268,33 @@ class DeconvHeadEval(nn.Module):
         self.joints = int(joints)
         self.feature_dtype = feature_dtype
         self.heatmaps = bool(heatmaps)
+        self.project = project is not None
+        if self.project:
+            project = ProjectionParams(*project)
+            self.register_buffer("proj_packed", project.packed)
+            self.register_buffer("proj_bias", project.bias)
 
     @classmethod
-    def from_reference(cls, backbone, device="cuda", feature_dtype=torch.bfloat16, heatmaps=True):
+    def from_reference(cls, backbone, device="cuda", feature_dtype=torch.bfloat16, heatmaps=True,
+                       process_features=None):
         """``backbone.deconv_layers`` (a Sequential of (ConvTranspose2d, BatchNorm2d, ReLU) triples, each
         k = 4, stride 2, padding 1, no output padding, no dilation, one group, 256 outputs) and
         ``backbone.final_layer`` (a Conv2d(256, J, 1), J <= 32); anything else raises and names what it
-        found."""
+        found.  ``process_features``: the volumetric model's ``Sequential`` of one ``Conv2d(256, 32, 1)``
+        (validated as ``VolumetricEval.from_reference`` does), run inside the last layer's launch."""
+        project = None
+        if process_features is not None:
+            _no_heatmaps_with_project(heatmaps)
+            pw, pb = _feature_conv_params(process_features)
+            if pw.shape[1] != COUT:
+                raise RuntimeError(f"process_features: expected Conv2d({COUT}, {FINAL_ROWS}, 1) behind the {COUT}-channel "
+                                   f"head, got in_channels={pw.shape[1]}")
+            project = pack_projection(pw, pb, device=device)
         triples = _deconv_triples(backbone.deconv_layers)
         w, b, J = _final_layer_params(backbone.final_layer)
         dev = torch.device(device)
         params = [fold_deconv_block(d, bn, device=dev) for d, bn, _ in triples]
-        return cls(params, w.to(dev), b.to(dev), J, feature_dtype, heatmaps)
+        return cls(params, w.to(dev), b.to(dev), J, feature_dtype, heatmaps, project)
 
     def layer_params(self, i):
         return DeconvParams(getattr(self, f"packed{i}"), getattr(self, f"scale{i}"), getattr(self, f"shift{i}"))
@@ -220,7 +309,9 @@ class DeconvHeadEval(nn.Module):
             h = torch.empty(h.shape, dtype=torch.bfloat16, device=x.device).copy_(h)   # the one cast-and-permute pass
         last = self.n_layers - 1
         for i in range(self.n_layers):
-            if i == last:
+            if i == last and self.project:
+                h = deconv4s2_project(h, self.layer_params(i), (self.proj_packed, self.proj_bias), self.feature_dtype)
+            elif i == last:
                 h = deconv4s2(h, self.layer_params(i), "nchw", self.feature_dtype)
             else:
                 h = deconv4s2(h, self.layer_params(i), "cl")
@@ -239,7 +330,8 @@ class BackboneEval(nn.Module):
     ``conv1`` ... ``layer4`` and optional ``alg_confidences`` / ``vol_confidences`` heads, kept as they are
     and called in the reference's order, then ``DeconvHeadEval``.  Returns the reference's 4-tuple
     ``(heatmaps, features, alg_confidences, vol_confidences)``, None where the backbone has no such
-    head (or ``heatmaps=False``).  The module adds no arithmetic of its own.  The trunk modules are
+    head (or ``heatmaps=False``); with ``process_features`` (``DeconvHeadEval``) the features are the
+    model's 32-channel ones.  The module adds no arithmetic of its own.  The trunk modules are
     the backbone's own objects (not copies) and must live on the device of the input; call under
     ``torch.no_grad()``."""
 
@@ -251,13 +343,14 @@ class BackboneEval(nn.Module):
         self.vol_confidences = vol_confidences
 
     @classmethod
-    def from_reference(cls, backbone, device="cuda", feature_dtype=torch.bfloat16, heatmaps=True):
+    def from_reference(cls, backbone, device="cuda", feature_dtype=torch.bfloat16, heatmaps=True,
+                       process_features=None):
         missing = [n for n in _TRUNK if not isinstance(getattr(backbone, n, None), nn.Module)]
         if missing:
             raise RuntimeError(f"BackboneEval: expected the trunk modules {', '.join(_TRUNK)}; {type(backbone).__name__} "
                                f"has no {', '.join(missing)}")
         trunk = nn.Sequential(*(getattr(backbone, n) for n in _TRUNK))
-        head = DeconvHeadEval.from_reference(backbone, device, feature_dtype, heatmaps)
+        head = DeconvHeadEval.from_reference(backbone, device, feature_dtype, heatmaps, process_features)
         return cls(trunk, head, getattr(backbone, "alg_confidences", None), getattr(backbone, "vol_confidences", None))
 
     def forward(self, x):

@@ -2,7 +2,8 @@
 kernels: ``process_features``, a ``Conv2d(256, 32, 1)``, as ``feature_conv``
 (csrc/feature_conv.hip), and ``VolumetricEval``, the one call from the backbone's
 feature maps to the joints: ``feature_conv``, ``v2v.unproject_channels_last`` and ``v2v.V2VEval``,
-composed and nothing else.
+composed and nothing else.  ``VolumetricModelEval`` puts ``backbone.BackboneEval`` in front of it:
+images to joints, with ``process_features`` optionally inside the head's last launch.
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ from .v2v import V2VEval, _inference_only, unproject_channels_last
 
 COUT = _ops.FEATURE_COUT
 MIN_CIN, MAX_CIN = 32, 512
+FUSED_DEFAULT = True          # VolumetricModelEval: the fused launch won every row of DESIGN.md §4.17
 
 
 def _check_cin(what, cin):
@@ -127,13 +129,71 @@ class VolumetricEval(nn.Module):
                         instead="the model's own modules, which autograd records")
         if features.dim() != 5:
             raise RuntimeError(f"VolumetricEval: features must be (B, N, Cin, H, W), got {tuple(features.shape)}")
+        if self.volume_aggregation_method == "conf_norm" and vol_confidences is None:
+            raise TypeError("volume_aggregation_method 'conf_norm' needs vol_confidences")      # before any launch
+        features = feature_conv(features, self.weight, self.bias, out_dtype=self.feature_dtype)
+        return self.from_projected(features, proj_matricies, coord_volumes, vol_confidences)
+
+    def from_projected(self, features32, proj_matricies, coord_volumes, vol_confidences=None):
+        """Everything of ``forward`` behind ``feature_conv``: features32 (B, N, 32, H, W), already through
+        ``process_features`` (``feature_conv``, or the head's ``deconv4s2_project``), and the other
+        arguments and the four return values of ``forward``."""
+        _inference_only("VolumetricEval", features32, vol_confidences,
+                        instead="the model's own modules, which autograd records")
+        if features32.dim() != 5 or features32.shape[2] != COUT:
+            raise RuntimeError(f"VolumetricEval: features32 must be (B, N, {COUT}, H, W), got {tuple(features32.shape)}")
+        features = features32
         method = self.volume_aggregation_method
         if method == "conf_norm":
             if vol_confidences is None:
                 raise TypeError("volume_aggregation_method 'conf_norm' needs vol_confidences")
             vol_confidences = vol_confidences / vol_confidences.sum(dim=1, keepdim=True)
-        features = feature_conv(features, self.weight, self.bias, out_dtype=self.feature_dtype)
         volumes = unproject_channels_last(features, proj_matricies, coord_volumes, method, out_dtype=torch.bfloat16,
                                           vol_confidences=vol_confidences, precision=self.precision)
         vol_keypoints_3d, volumes = self.v2v(volumes, coord_volumes, self.volume_multiplier, self.volume_softmax)
         return vol_keypoints_3d, features, volumes, vol_confidences
+
+
+class VolumetricModelEval(nn.Module):
+    """``VolumetricTriangulationNet.forward`` (triangulation.py:245-355) from the images to the joints,
+    eval mode: ``backbone.BackboneEval`` over ``model.backbone`` on the images as (B * N, 3, H, W), then
+
+    - ``fused=True``: the head's last layer ran ``process_features`` in its own launch
+      (``deconv4s2_project``), and ``VolumetricEval.from_projected`` takes the 32-channel features;
+    - ``fused=False``: ``VolumetricEval.forward`` on the 256-channel features.
+
+    ``module(images (B, N, 3, H, W), proj_matricies (B, N, 3, 4), coord_volumes (B, V, V, V, 3) or a
+    volumetric.Cuboids)`` returns ``VolumetricEval``'s four values.  The projection matrices are the
+    caller's, already at the feature maps' resolution (triangulation.py:271-278).  The module adds no
+    arithmetic of its own; the backbone's heatmaps are not computed.  Inference-only."""
+
+    def __init__(self, backbone, volumetric, fused):
+        super().__init__()
+        self.backbone = backbone
+        self.volumetric = volumetric
+        self.fused = bool(fused)
+
+    @classmethod
+    def from_reference(cls, model, device="cuda", feature_dtype=torch.bfloat16, half_res="kernels", deep="kernels",
+                       precision=None, fused=FUSED_DEFAULT):
+        """``model.backbone`` through ``BackboneEval.from_reference`` (``heatmaps=False``; with ``fused`` it
+        is given ``model.process_features``) and the rest of ``model`` through
+        ``VolumetricEval.from_reference``.  ``fused`` defaults to what was measured faster (DESIGN.md
+        §4.17)."""
+        from .backbone import BackboneEval
+        vol = VolumetricEval.from_reference(model, device, feature_dtype, half_res, deep, precision)
+        bb = BackboneEval.from_reference(model.backbone, device, feature_dtype, heatmaps=False,
+                                         process_features=model.process_features if fused else None)
+        return cls(bb, vol, fused)
+
+    def forward(self, images, proj_matricies, coord_volumes):
+        _inference_only("VolumetricModelEval", images, instead="the model itself, which autograd records")
+        if images.dim() != 5:
+            raise RuntimeError(f"VolumetricModelEval: images must be (B, N, 3, H, W), got {tuple(images.shape)}")
+        B, N = images.shape[:2]
+        _, features, _, vol_confidences = self.backbone(images.reshape(B * N, *images.shape[2:]))
+        features = features.view(B, N, *features.shape[1:])
+        if vol_confidences is not None:
+            vol_confidences = vol_confidences.view(B, N, *vol_confidences.shape[1:])
+        run = self.volumetric.from_projected if self.fused else self.volumetric
+        return run(features, proj_matricies, coord_volumes, vol_confidences)

@@ -1,7 +1,7 @@
 """Device time of the backbone's deconv head on kernels (csrc/deconv_head.hip, mvn_rocm/backbone.py)
 against the reference's own ``deconv_layers`` + ``final_layer`` modules run by torch on the same box.
 
-    python tools/time_deconv_head.py [--frames 8,32] [--repeats 5] [--calls 20] [--out FILE]
+    python tools/time_deconv_head.py [--frames 8,32] [--repeats 5] [--calls 20] [--out FILE] [--project]
 
 The method of tools/time_feature_conv.py: per measurement 10 warm-up calls, then HIP events around
 `calls` back-to-back calls; the paths alternate in one process, `repeats` measurements each; the
@@ -17,7 +17,12 @@ algorithmic bytes (x once, y once, the weight once).
 
 Head rows: DeconvHeadEval.forward on layer4's (4 B, 2048, 12, 12) output, features only and with the
 heatmaps (J = 17), from an f32 input in the default format and from a bf16 channels_last input,
-against torch's deconv_layers (and final_layer) in its two forms."""
+against torch's deconv_layers (and final_layer) in its two forms.
+
+--project prints another table instead: the last layer with the volumetric model's
+process_features (a Conv2d(256, 32, 1)) behind it, as the parent's two launches (deconv4s2 to NCHW,
+then model.feature_conv) against the one launch of deconv4s2_project, for bf16 and f32 features, and
+the whole head (bf16 channels_last in) followed by feature_conv against the head with ``project``."""
 import argparse
 import os
 import statistics
@@ -29,7 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 from torch import nn  # noqa: E402
 
-from mvn_rocm import backbone  # noqa: E402
+from mvn_rocm import backbone, model  # noqa: E402
 from time_v2v_res3d import measure  # noqa: E402
 
 N, C4, H4, COUT, J = 4, 2048, 12, 256, 17
@@ -69,6 +74,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--project", action="store_true", help="the fused projection against the two launches")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     out = None
@@ -90,6 +96,11 @@ def main():
         return {k: (statistics.median(v), max(v) - min(v)) for k, v in res.items()}
 
     bf16, cl = torch.bfloat16, torch.channels_last
+    if args.project:
+        project_table(args, dev, emit, alternate)
+        if out:
+            out.close()
+        return
     emit(f"# deconv head: 3 x (ConvTranspose2d(Cin, {COUT}, 4, 2, 1) + BN + ReLU) on B x {N} maps of {C4} x {H4}^2, final_layer to "
          f"J = {J}; {args.repeats} repeats x {args.calls} calls after 10 warm-up calls, paths alternating in one process; "
          f"median us per call (device, HIP events), spread = range of the repeats")
@@ -148,6 +159,53 @@ def main():
             torch.cuda.empty_cache()
     if out:
         out.close()
+
+
+def project_table(args, dev, emit, alternate):
+    """Layer 3 + process_features, unfused (two launches) against fused (one), and the head both ways."""
+    bf16, cl = torch.bfloat16, torch.channels_last
+    emit(f"# last deconv layer ({COUT} x {4 * H4}^2 -> {COUT} x {8 * H4}^2) + Conv2d({COUT}, 32, 1) on B x {N} maps: unfused = deconv4s2 "
+         f"(NCHW) then feature_conv, fused = deconv4s2_project; head = DeconvHeadEval from a bf16 channels_last layer4 output; "
+         f"{args.repeats} repeats x {args.calls} calls after 10 warm-up calls, paths alternating in one process; median us per "
+         f"call (device, HIP events), spread = range of the repeats")
+    emit(f"# {torch.cuda.get_device_name(0)}; difference - spreads = unfused - fused - both spreads: positive means the fused "
+         f"launch wins by more than the sum of the two ranges")
+    net = init(Head())
+    pf = init(nn.Sequential(nn.Conv2d(COUT, 32, 1)))
+    with torch.no_grad():
+        params = [backbone.fold_deconv_block(net.deconv_layers[3 * i], net.deconv_layers[3 * i + 1], device=dev) for i in range(3)]
+        pw, pb = pf[0].weight.detach().reshape(32, COUT).to(dev), pf[0].bias.detach().to(dev)
+        proj = backbone.pack_projection(pw, pb, device=dev)
+        emit(f"{'row':<28} {'B':>3} {'features':>8} {'unfused us':>10} {'spread':>7} {'fused us':>9} {'spread':>7} "
+             f"{'unfused / fused':>15} {'difference - spreads':>20}")
+
+        def row(name, B, dt, r):
+            (u, us), (f, fs) = r["unfused"], r["fused"]
+            emit(f"{name:<28} {B:>3} {str(dt).replace('torch.', ''):>8} {u:>10.1f} {us:>7.1f} {f:>9.1f} {fs:>7.1f} {u / f:>15.3f} "
+                 f"{u - f - us - fs:>20.1f}")
+
+        for B in args.frames:
+            M = B * N
+            g = torch.Generator().manual_seed(B)
+            xk = torch.randn((M, 4 * H4, 4 * H4, COUT), generator=g).to(dev).to(bf16)
+            x16 = torch.randn((M, C4, H4, H4), generator=g).to(dev).to(bf16).contiguous(memory_format=cl)
+            r = alternate({"unfused": lambda: backbone.deconv4s2(xk, params[2], "nchw"),
+                           "fused": lambda: backbone.deconv4s2(xk, params[2], "nchw")})
+            row("layer 3 alone, twice", B, bf16, r)
+            for dt in (bf16, torch.float32):
+                r = alternate({"unfused": lambda: model.feature_conv(backbone.deconv4s2(xk, params[2], "nchw", dt), pw, pb,
+                                                                     out_dtype=dt),
+                               "fused": lambda: backbone.deconv4s2_project(xk, params[2], proj, dt)})
+                row("layer 3 + process_features", B, dt, r)
+            for dt in (bf16, torch.float32):
+                plain = backbone.DeconvHeadEval.from_reference(net, device=dev, feature_dtype=dt, heatmaps=False)
+                fused = backbone.DeconvHeadEval.from_reference(net, device=dev, feature_dtype=dt, heatmaps=False,
+                                                               process_features=pf)
+                r = alternate({"unfused": lambda: model.feature_conv(plain(x16)[1], pw, pb, out_dtype=dt),
+                               "fused": lambda: fused(x16)[1]})
+                row("head + process_features", B, dt, r)
+            del xk, x16
+            torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":
