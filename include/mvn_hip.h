@@ -835,7 +835,9 @@ int mvn_algebraic_triangulate(const void* heatmaps, int dtype, float multiplier,
  *   lds_slots  > 0: LDS slot budget per staging pass of the tiled kernel (small budgets
  *              force the multi-pass and global-gather paths); 0 = the kernel's own budget
  *   kernel     0 = default dispatch, 1 = the simple register-geometry kernel,
- *              2 = the generic tiled kernel (skip the four-view kernel)
+ *              2 = the generic tiled kernel (skip the four-view kernel),
+ *              3 = the four-view kernel with 16-byte LDS slots (its f32 channels-last shape)
+ *                  where the default dispatch takes the 8-byte slots (4 views, f32, NCDHW, exact)
  * Returns MVN_OK, or MVN_ERR_ARG for a negative budget or an unknown kernel.
  */
 int mvn_debug_set_unproject(int lds_slots, int kernel);
@@ -862,6 +864,15 @@ int mvn_debug_dassert_selftest(int n, void* stream);
  * bf16 (1) feature maps.  Needs a device; returns a count >= 1.
  */
 int mvn_debug_unproject_occupancy(int bf16_maps);
+
+/*
+ * Diagnostics: the same count for the f32 softmax kernel of one tile shape of the four-view
+ * kernel (csrc/unproject_x4.hip): shape 0 = 16-byte LDS slots, 5 = 8-byte slots.
+ * *private_bytes receives the kernel's private-segment (scratch) size per work-item and
+ * *registers its register count, both from hipFuncGetAttributes.  Needs a device.  Returns the
+ * count, MVN_ERR_ARG for another shape or a null pointer, MVN_ERR_LAUNCH if a query fails.
+ */
+int mvn_debug_x4_shape_occupancy(int shape, int* private_bytes, int* registers);
 
 /*
  * Diagnostics, host only (no device needed): the block -> tile order of the four-view

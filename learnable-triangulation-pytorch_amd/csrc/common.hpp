@@ -125,6 +125,7 @@ const bool g_dassert_registered = (dassert_registry().push_back(&dassert_read_cl
 int unproject_lds_slot_budget();   // 0 = the kernel's own budget
 bool unproject_force_simple();
 bool unproject_force_generic();    // skip the four-view kernel (unproject_x4.hip)
+bool unproject_force_wide_slots(); // four views, f32: 16-byte slots (X4Shape<0>) where <5> would run
 
 // XCD-aware block order (cdna_hip_programming.md §5.5 T1, bijective form): hardware deals
 // blocks round-robin over the 8 XCDs, so block b runs on XCD b % 8.  Remapping gives each

@@ -22,11 +22,17 @@ std::atomic<int> g_lds_slots{0}, g_force_simple{0};
 int unproject_lds_slot_budget() { return g_lds_slots.load(std::memory_order_relaxed); }
 bool unproject_force_simple() { return g_force_simple.load(std::memory_order_relaxed) == 1; }
 bool unproject_force_generic() { return g_force_simple.load(std::memory_order_relaxed) == 2; }
+bool unproject_force_wide_slots() { return g_force_simple.load(std::memory_order_relaxed) == 3; }
 
 }  // namespace mvn
 
 extern "C" int mvn_debug_unproject_occupancy(int bf16_maps) {
   return mvn::unproj::x4_blocks_per_cu(bf16_maps ? 1 : 0);
+}
+
+extern "C" int mvn_debug_x4_shape_occupancy(int shape, int* private_bytes, int* registers) {
+  if ((shape != 0 && shape != 5) || !private_bytes || !registers) return MVN_ERR_ARG;
+  return mvn::unproj::x4_shape_occupancy(shape, private_bytes, registers);
 }
 
 extern "C" int mvn_debug_x4_image_slots(int shape) {
@@ -67,7 +73,7 @@ extern "C" int mvn_debug_device_asserts(int* enabled, unsigned* count, unsigned*
 }
 
 extern "C" int mvn_debug_set_unproject(int lds_slots, int kernel) {
-  if (lds_slots < 0 || kernel < 0 || kernel > 2) return MVN_ERR_ARG;
+  if (lds_slots < 0 || kernel < 0 || kernel > 3) return MVN_ERR_ARG;
   mvn::g_lds_slots.store(lds_slots, std::memory_order_relaxed);
   mvn::g_force_simple.store(kernel, std::memory_order_relaxed);
   return MVN_OK;

@@ -284,6 +284,23 @@ __device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elemen
 // (w2, w3) pairs, 2 VGPRs per view-pair of weights instead of a {w, w} copy per weight.
 template <int K> __device__ __forceinline__ f2 splat(f2 p) { return __builtin_shufflevector(p, p, K, K); }
 
+// a * {w[K], w[K]} and fma(a, {w[K], w[K]}, c) with the broadcast written into the instruction:
+// for a weight pair in VGPRs the backend materialises the {w, w} copy after all (16 pairs, 32
+// VGPRs for four views), which the 80-register budget of 6 waves per SIMD has no room for.
+// Lane-wise the same IEEE mul / fma as splat<K> with operator* / pk_fma.  Not volatile.
+template <int K> __device__ __forceinline__ f2 pk_mul_sel(f2 a, f2 w) {
+  f2 r;
+  if constexpr (K == 0) asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(w));
+  else asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(w));
+  return r;
+}
+template <int K> __device__ __forceinline__ f2 pk_fma_sel(f2 a, f2 w, f2 c) {
+  f2 r;
+  if constexpr (K == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "v"(w), "v"(c));
+  else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(w), "v"(c));
+  return r;
+}
+
 template <typename TIn> struct ChunkT;               // 4 pixels of one channel plane
 template <> struct ChunkT<float> { using type = uint4; };
 template <> struct ChunkT<uint16_t> { using type = uint2; };
@@ -499,6 +516,7 @@ template <int AGG, typename TIn, typename TOut> int launch_tiled(const UnprojCal
 template <int AGG, typename TIn, typename TOut> int launch_x4(const UnprojCall& c);
 // Diagnostics (mvn_debug_unproject_occupancy): resident blocks per CU of the softmax kernels.
 int x4_blocks_per_cu(int bf16);
+int x4_shape_occupancy(int shape, int* private_bytes, int* registers);
 // ... (mvn_debug_x4_block_tiles / mvn_debug_x4_image_slots): the X4Order the four-view kernel is
 // built with, and the image slots of one LDS pass of its f32 (0), bf16 (1) or 8-view (2) shape.
 int x4_launch_order();

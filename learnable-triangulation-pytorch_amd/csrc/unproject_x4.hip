@@ -1,6 +1,7 @@
 // Chunk-staged unprojection for gfx950 — the production kernel behind mvn_unproject for the
 // configurations of BASELINE.json: 4 views (W % 4 == 0, C % 4 == 0; 16-byte LDS slots of 4
-// channels) and 8 views (config 4: W % 4 == 0, C % 2 == 0, NCDHW; 8-byte slots of 2).
+// channels, or 8-byte slots of 2 for f32 maps into NCDHW f32 in exact arithmetic) and 8 views
+// (config 4: W % 4 == 0, C % 2 == 0, NCDHW; 8-byte slots of 2).
 //
 // Contract and numerics: mvn/utils/op.py:99-163 exactly as unproject_tiled.hip (sum / max /
 // conf bit-exact with the reference; softmax max-first with exp2 and one reciprocal, same
@@ -82,6 +83,24 @@ template <> struct X4Shape<3> {
 // profiles/r21_ab_tile_occupancy_negatives.txt)
 template <> struct X4Shape<4> {
   static constexpr int NV = 4, G = 4, TX = 8, TY = 8, TZ = 8, THREADS = 512, SLOTS = 1536, MC = 1, WAVES = 6;
+  static constexpr int STORE_F32 = kStorePolicyF32;
+};
+
+// 4 views, f32 maps, NCDHW f32 output, exact arithmetic (config 2): shape 0's tile, footprints
+// and pass limit on 8-byte slots of 2 channels.  Every group-width register of the channel loop
+// halves (staged chunks, taps in flight, samples, outputs) and the weight pairs are broadcast by
+// op_sel (pk_mul_sel / pk_fma_sel) instead of living as 16 splatted pairs: 71 VGPRs, no scratch,
+// against shape 0's 117.  Two buffers are 38,912 bytes, so three blocks fit the CU: 6 waves per
+// SIMD.  The price is 16 barriers per tile for 8 and twice the LDS instructions at half the width.
+// Measured (r24, profiles/r24_*): kernel mean 139.7 -> 130.2 us (rocprofv3), 142.4-147.5 ->
+// 132.1 us back to back (tools/ab_lib.py); VALU busy per SIMD 78 % -> 89 %, wave life 8,731 ->
+// 11,720 quad-cycles.  The launch is 5.33 rounds of 768 resident blocks, not 8.0 of 512: the
+// schedule model (tools/schedule_model.py --blocks-per-cu 3) puts its efficiency at 0.86 for 0.92.
+// Masked-off pixels of a chunk branch as in shape 0 (their trash-slot form: 143.9 us against
+// 136.6); two views' taps in flight (one: 144.5 us, all four: 140.5 against 135.4).  The arithmetic
+// per channel pair is shape 0's, bit for bit.
+template <> struct X4Shape<5> {
+  static constexpr int NV = 4, G = 2, TX = 4, TY = 8, TZ = 16, THREADS = 512, SLOTS = 2432, MC = 2, WAVES = 6;
   static constexpr int STORE_F32 = kStorePolicyF32;
 };
 
@@ -429,9 +448,9 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
 #pragma unroll
     for (int k = 0; k < G; ++k) pre[k] = load_chunk<TIn>(frs, goff, uint32_t((c0 + k) * HW) * E);
   };
-  // masked-off pixels: bf16 maps and 2-channel slots write them to the lane's trash slot
-  // (no exec-mask branch per write), f32 maps on 4-channel slots branch (A/B at the bench
-  // configs: each is the faster for its case; 8 views 694 -> 677 us, r16)
+  // masked-off pixels: bf16 maps and the 8-view 2-channel slots write them to the lane's trash
+  // slot (no exec-mask branch per write), f32 maps at 4 views branch (A/B at the bench configs:
+  // each is the faster for its case; 8 views 694 -> 677 us, r16; X4Shape<5> 143.9 -> 136.6 us, r24)
   auto write_group = [&](Slot* buf, const Chunk (&pre)[G], int s0, uint32_t mask) __attribute__((always_inline)) {
     if constexpr (PAIR) {
       // chunk dwords: lo = (px0, px1), hi = (px2, px3) of one channel; pixels 4, 5 are the
@@ -459,7 +478,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
       else
         q = make_uint2(chunk_px(pre[0], p), chunk_px(pre[1], p));
       MVN_DASSERT(!(mask & (1u << p)) || (s0 + p >= 0 && s0 + p < kTrash));   // a box slot, not trash / zero
-      if constexpr (sizeof(TIn) == 2 || G == 2)
+      if constexpr (sizeof(TIn) == 2 || (G == 2 && NV == 8))
         buf[(mask & (1u << p)) ? s0 + p : kTrash + lane] = q;
       else if (mask & (1u << p))
         buf[s0 + p] = q;
@@ -481,6 +500,8 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
       return *reinterpret_cast<const Slot*>(p);
     }
   };
+  // 4 views on 2-channel slots (X4Shape<5>): the weight pairs broadcast by op_sel
+  constexpr bool kSelWeights = NV == 4 && G == 2;
   // sample the views staged in an LDS buffer (all, or those of `pass`) into channel pairs
   auto sample_views = [&](const char* buf, bool all, int pass, f2 (&sv)[NP][NV]) __attribute__((always_inline)) {
 #pragma unroll
@@ -508,6 +529,13 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
       const Slot bq = tap(buf + anw[v] + kSlotB);
       const Slot cq = tap(buf + asw[v]);
       const Slot d = tap(buf + asw[v] + kSlotB);
+      if constexpr (kSelWeights) {
+        sv[0][v] = pk_fma_sel<1>(slot_pair(d, 0), wp[v][1],
+                                 pk_fma_sel<0>(slot_pair(cq, 0), wp[v][1],
+                                               pk_fma_sel<1>(slot_pair(bq, 0), wp[v][0], pk_mul_sel<0>(slot_pair(a, 0), wp[v][0]))));
+        if (v & 1) __builtin_amdgcn_sched_barrier(0);   // at most two views' taps in flight
+        continue;
+      }
       const f2 w0 = splat<0>(wp[v][0]), w1 = splat<1>(wp[v][0]), w2 = splat<0>(wp[v][1]), w3 = splat<1>(wp[v][1]);
 #pragma unroll
       for (int q = 0; q < NP; ++q)
@@ -648,9 +676,10 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // fast: the tap offsets before the staging starts, so that the per-view base pixels die here
-  // (live into the multi-pass branch they spilled at 6 waves per SIMD)
-  if constexpr (FAST != 0) tap_slots();
+  // fast, and every shape at 6 waves per SIMD: the tap offsets before the staging starts, so that
+  // the per-view base pixels die here (live into the multi-pass branch they spilled at 6 waves)
+  constexpr bool kTapsFirst = FAST != 0 || S::WAVES == 6;
+  if constexpr (kTapsFirst) tap_slots();
   if (npass == 1) {
     // ---- one pass: up to MC chunks per thread (chunk t + kThreads * i over the views'
     // concatenated chunk ranges), two LDS buffers, the next group's loads in flight --------
@@ -679,7 +708,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
         if (wfirst + kWaves * kLanesW * i < total) write_group(buf, pre[i], s0[i], mask[i]);
     };
     issue(0);
-    if constexpr (FAST == 0) tap_slots();
+    if constexpr (!kTapsFirst) tap_slots();
     commit(stageA);
     __syncthreads();
     // A group's outputs are stored after the NEXT group's commit: on gfx950 vmcnt counts
@@ -708,7 +737,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
   }
 
   // ---- several passes of whole views per channel group (close cameras) ---------------
-  if constexpr (FAST == 0) tap_slots();
+  if constexpr (!kTapsFirst) tap_slots();
   for (int c0 = 0; c0 < C; c0 += G) {
     f2 sv[NP][NV];
     for (int pass = 0; pass < npass; ++pass) {
@@ -771,6 +800,10 @@ int launch_x4(const UnprojCall& c) {
   };
   if (eight) return go(std::integral_constant<int, 3>{}, I0{});
   using K4 = std::integral_constant<int, sizeof(TIn) == 2 ? 2 : 0>;
+  // f32 maps, NCDHW, exact arithmetic: 2-channel slots at 6 waves per SIMD (X4Shape<5>), unless
+  // the test knob asks for the 16-byte slots
+  if constexpr (sizeof(TIn) == 4 && sizeof(TOut) == 4)
+    if (!c.out_cl && !c.fast && !unproject_force_wide_slots()) return launch(std::integral_constant<int, 5>{}, I0{}, I0{});
   return c.out_cl ? go(K4{}, I1{}) : go(K4{}, I0{});
 }
 
@@ -783,6 +816,23 @@ int x4_blocks_per_cu(int bf16) {
            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, unproject_x4<MVN_AGG_SOFTMAX, float, float, 0, 0, 0>,
                                                           X4Shape<0>::THREADS, 0);
   return e == hipSuccess ? n : MVN_ERR_LAUNCH;
+}
+
+// mvn_debug_x4_shape_occupancy: the same for the f32 softmax kernel of X4Shape<0> or <5>, with the
+// kernel's private-segment bytes and register count
+int x4_shape_occupancy(int shape, int* private_bytes, int* registers) {
+  auto query = [&](auto kernel, int threads) {
+    int n = 0;
+    hipFuncAttributes a;
+    if (hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel)) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0) != hipSuccess)
+      return int(MVN_ERR_LAUNCH);
+    *private_bytes = int(a.localSizeBytes);
+    *registers = a.numRegs;
+    return n;
+  };
+  return shape == 5 ? query(unproject_x4<MVN_AGG_SOFTMAX, float, float, 5, 0, 0>, X4Shape<5>::THREADS)
+                    : query(unproject_x4<MVN_AGG_SOFTMAX, float, float, 0, 0, 0>, X4Shape<0>::THREADS);
 }
 
 int x4_launch_order() { return kX4Order; }

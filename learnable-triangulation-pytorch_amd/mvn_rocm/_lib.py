@@ -114,7 +114,8 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_uint)]),
     "mvn_debug_dassert_selftest": (_c_int, [_c_int, _c_void_p]),
     "mvn_debug_unproject_occupancy": (_c_int, [_c_int]),
-    "mvn_debug_x4_block_tiles": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_int)]),
+    "mvn_debug_x4_shape_occupancy": (_c_int, [_c_int, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
+    "mvn_debug_x4_block_tiles":(_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_int)]),
     "mvn_debug_x4_image_slots": (_c_int, [_c_int]),
     "mvn_debug_dlt_trace": (_c_int, [_c_void_p] * 6 + [_c_int, _c_int, _c_int, _c_void_p]),
 }
@@ -154,8 +155,8 @@ class unproject_knobs:
     """Context manager (tests only): force unprojection paths through the C ABI's test hook
     ``mvn_debug_set_unproject`` and restore the defaults on exit."""
 
-    def __init__(self, lds_slots: int = 0, simple: bool = False, generic: bool = False):
-        self.args = (int(lds_slots), 1 if simple else 2 if generic else 0)
+    def __init__(self, lds_slots: int = 0, simple: bool = False, generic: bool = False, wide_slots: bool = False):
+        self.args = (int(lds_slots), 1 if simple else 2 if generic else 3 if wide_slots else 0)
 
     def __enter__(self):
         check(load().mvn_debug_set_unproject(*self.args), "mvn_debug_set_unproject")

@@ -8,7 +8,8 @@ slots (32 CUs x 2 resident blocks) greedily in block order.  A block costs
 (1 - d) + d * chunks / mean, times s for a multi-pass tile.  Efficiency = sum of the costs /
 (8 * 64 * makespan).  The orders are the library's own (mvn_debug_x4_block_tiles), so the tool,
 the tests and the kernel share one definition; simulate() takes any block -> tile array.
-    python tools/schedule_model.py [--frames 8] [--slots N] [--s 2.0]"""
+--blocks-per-cu 3 replays it for the 2-channel-slot shape (X4Shape<5>: 96 block slots per XCD).
+    python tools/schedule_model.py [--frames 8] [--slots N] [--s 2.0] [--blocks-per-cu 2]"""
 import argparse
 import ctypes
 import heapq
@@ -96,7 +97,10 @@ def main():
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--slots", type=int, default=0, help="image slots of a pass (default: the library's)")
     ap.add_argument("--s", type=float, default=2.0, help="cost of a multi-pass tile in one-pass tiles")
+    ap.add_argument("--blocks-per-cu", type=int, default=2, help="resident blocks per CU (32 CUs per XCD)")
     a = ap.parse_args()
+    global SLOTS_PER_XCD
+    SLOTS_PER_XCD = 32 * a.blocks_per_cu
     lim = a.slots or image_slots()
     fx, fy, ok = lds_conflicts.geometry(B=a.frames)
     chunks, slots, passes = tiles(fx, fy, ok, lim)
