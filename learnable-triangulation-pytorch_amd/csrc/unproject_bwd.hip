@@ -12,7 +12,8 @@
 // projection matrices and coordinate volumes are not produced (the reference's callers
 // build both from numpy constants: triangulation.py:272-341).
 //
-// Structure mirrors the forward kernel: a block owns a 4x8x8 voxel tile, stages the
+// Structure mirrors the forward kernel (the footprint prologue is shared with it:
+// unproject_footprint.hpp): a block owns a 4x8x8 voxel tile, stages the
 // forward features of its footprint when the aggregation needs samples, accumulates the
 // tile's tap contributions into an LDS copy of the footprint with ds_add_f32, and flushes
 // it with one global float atomic per touched (pixel, channel) — ~10x fewer global atomics
@@ -39,7 +40,7 @@
 // ATen's grid_sampler backward confines a NaN to the taps it touches.
 #include <algorithm>
 
-#include "unproject_common.hpp"
+#include "unproject_footprint.hpp"
 
 namespace mvn {
 namespace unproj {
@@ -115,10 +116,10 @@ __global__ __launch_bounds__(kThreads) void unproject_bwd_tiled(
   __shared__ float4 gacc[DET ? 1 : kSlots];  // gradient accumulator (channels-last)
   __shared__ unsigned long long gq[DET ? kSlots * G : 1];   // the same in fixed point (DET)
   __shared__ int red[kWaves][NV][4];
-  __shared__ int region[NV][5];              // xs, ys, bw, pitch, base
+  __shared__ int region[NV][kRegionWords];
   __shared__ float gconf_acc[NV][G];
   __shared__ unsigned long long gconf_q[DET ? NV : 1][G];
-  __shared__ int info[2];                    // total slots (or -1: direct global path)
+  __shared__ int info[2];                    // [1]: total slots (or -1: direct global path)
 
   const int nTx = (Vx + TX - 1) / TX, nTy = (Vy + TY - 1) / TY, nTz = (Vz + TZ - 1) / TZ;
   int L = xcd_remap(blockIdx.x, B * nTx * nTy * nTz);
@@ -139,54 +140,19 @@ __global__ __launch_bounds__(kThreads) void unproject_bwd_tiled(
 
   if (t < 2) { fstage[kZero + t] = make_float4(0.f, 0.f, 0.f, 0.f); }
 
-  int fx[NV], fy[NV];
-  float w[NV][4];
-  bool has[NV];
-  int bb[NV][4];
+  int fx[NV] = {}, fy[NV] = {};
+  float w[NV][4] = {};
+  bool has[NV] = {};
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
-    bb[v][0] = INT_MAX; bb[v][1] = INT_MIN; bb[v][2] = INT_MAX; bb[v][3] = INT_MIN;
-    has[v] = false; fx[v] = fy[v] = 0; w[v][0] = w[v][1] = w[v][2] = w[v][3] = 0.f;
-    if (v < N) {
-      const Proj p = project(Pb + v * 12, cx, cy, cz, H, W, align_corners);
-      const float fx0 = floorf(p.ix), fy0 = floorf(p.iy);
-      const bool h = act & !p.invalid & (fx0 >= -1.f) & (fx0 < float(W)) & (fy0 >= -1.f) & (fy0 < float(H));
-      if (h) {
-        const float a = p.ix - fx0, c = p.iy - fy0;
-        w[v][0] = (1.f - c) * (1.f - a); w[v][1] = (1.f - c) * a; w[v][2] = c * (1.f - a); w[v][3] = c * a;
-        fx[v] = int(fx0); fy[v] = int(fy0);
-        bb[v][0] = fx[v]; bb[v][1] = fx[v]; bb[v][2] = fy[v]; bb[v][3] = fy[v];
-      }
-      has[v] = h;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      bb[v][0] = min(bb[v][0], __shfl_xor(bb[v][0], o, kWave));
-      bb[v][1] = max(bb[v][1], __shfl_xor(bb[v][1], o, kWave));
-      bb[v][2] = min(bb[v][2], __shfl_xor(bb[v][2], o, kWave));
-      bb[v][3] = max(bb[v][3], __shfl_xor(bb[v][3], o, kWave));
-    }
-    if (lane == 0) { red[wid][v][0] = bb[v][0]; red[wid][v][1] = bb[v][1]; red[wid][v][2] = bb[v][2]; red[wid][v][3] = bb[v][3]; }
+    if (v >= N) break;
+    has[v] = footprint_base(project(Pb + v * 12, cx, cy, cz, H, W, align_corners), act, H, W, fx[v], fy[v], w[v]);
+    wave_box(has[v], fx[v], fy[v], lane, red[wid][v]);
   }
   __syncthreads();
-  if (t == 0) {
-    int next = 0;
-    for (int v = 0; v < NV && v < N; ++v) {
-      int x0 = INT_MAX, x1 = INT_MIN, y0 = INT_MAX, y1 = INT_MIN;
-      for (int q = 0; q < kWaves; ++q) {
-        x0 = min(x0, red[q][v][0]); x1 = max(x1, red[q][v][1]);
-        y0 = min(y0, red[q][v][2]); y1 = max(y1, red[q][v][3]);
-      }
-      int bw = 0, bh = 0;
-      if (x0 <= x1) { bw = x1 - x0 + 2; bh = y1 - y0 + 2; }
-      const int pitch = bw | 1;
-      region[v][0] = x0; region[v][1] = y0; region[v][2] = bw; region[v][3] = pitch; region[v][4] = next;
-      next += pitch * bh;
-    }
-    info[0] = next <= kZero ? next : -1;
-  }
+  if (t == 0) layout_regions(red, region, info, N, kZero, 1);      // one pass, or the direct global path
   __syncthreads();
-  const int total = __builtin_amdgcn_readfirstlane(info[0]);
+  const int total = __builtin_amdgcn_readfirstlane(info[1]);
 
   const TG* gb = gout + size_t(b) * C * nvox + vox;
   if (total < 0) {
@@ -249,18 +215,12 @@ __global__ __launch_bounds__(kThreads) void unproject_bwd_tiled(
     return;
   }
 
-  int rx[NV], ry[NV], rbw[NV], rpitch[NV], rbase[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    rx[v] = __builtin_amdgcn_readfirstlane(region[v][0]);
-    ry[v] = __builtin_amdgcn_readfirstlane(region[v][1]);
-    rbw[v] = __builtin_amdgcn_readfirstlane(region[v][2]);
-    rpitch[v] = __builtin_amdgcn_readfirstlane(region[v][3]);
-    rbase[v] = __builtin_amdgcn_readfirstlane(region[v][4]);
-  }
+  const auto rg = load_regions(region);
+  // the north-west tap's slot; the south-west one is a row on (formed on use: NV registers less)
   int slot[NV];
 #pragma unroll
-  for (int v = 0; v < NV; ++v) slot[v] = has[v] ? rbase[v] + (fy[v] - ry[v]) * rpitch[v] + (fx[v] - rx[v]) : kZero;
+  for (int v = 0; v < NV; ++v)
+    slot[v] = tap_slot(has[v], fx[v], fy[v], rg.x[v], rg.y[v], rg.pitch[v], rg.base[v], kZero);
 
   for (int c0 = 0; c0 < C; c0 += G) {
     // ---- zero the accumulator, stage forward features ---------------------------------
@@ -272,19 +232,11 @@ __global__ __launch_bounds__(kThreads) void unproject_bwd_tiled(
         gacc[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
       if constexpr (kNeedSamples) {
-        int v = 0;
-#pragma unroll
-        for (int u = 1; u < NV; ++u) if (u < N && idx >= rbase[u]) v = u;
-        int px = 0, py = 0, bwv = 0, pv = 1, xs = 0, ys = 0, base = 0;
-#pragma unroll
-        for (int u = 0; u < NV; ++u) if (u == v) { pv = rpitch[u]; bwv = rbw[u]; xs = rx[u]; ys = ry[u]; base = rbase[u]; }
-        py = (idx - base) / pv;
-        px = idx - base - py * pv;
-        const int gx = xs + px, gy = ys + py;
-        const bool in = (px < bwv) & (gx >= 0) & (gx < W) & (gy >= 0) & (gy < H);
+        const SlotPixel p = slot_pixel(idx, 0, N, rg, H, W);
         float q[G];
 #pragma unroll
-        for (int k = 0; k < G; ++k) q[k] = (in && c0 + k < C) ? ldf(fb, (size_t(v) * C + c0 + k) * HW + size_t(gy) * W + gx) : 0.f;
+        for (int k = 0; k < G; ++k)
+          q[k] = (p.in && c0 + k < C) ? ldf(fb, (size_t(p.view) * C + c0 + k) * HW + size_t(p.gy) * W + p.gx) : 0.f;
         MVN_DASSERT(idx >= 0 && idx < kZero);
         fstage[idx] = make_float4(q[0], q[1], q[2], q[3]);
       }
@@ -309,14 +261,14 @@ __global__ __launch_bounds__(kThreads) void unproject_bwd_tiled(
       for (int k = 0; k < G; ++k) s[v][k] = 0.f;
       if constexpr (kNeedSamples) {
         if (v < N) {
-          const int o = slot[v], o2 = has[v] ? slot[v] + rpitch[v] : kZero;
+          const int o = slot[v], o2 = has[v] ? slot[v] + rg.pitch[v] : kZero;
           MVN_DASSERT(o >= 0 && o + 1 < kSlots && o2 >= 0 && o2 + 1 < kSlots);
           const float4 a = fstage[o], bq = fstage[o + 1], c = fstage[o2], d = fstage[o2 + 1];
           const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {bq.x, bq.y, bq.z, bq.w};
           const float cv[4] = {c.x, c.y, c.z, c.w}, dv[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
           for (int k = 0; k < G; ++k)
-            s[v][k] = __builtin_fmaf(dv[k], w[v][3], __builtin_fmaf(cv[k], w[v][2], __builtin_fmaf(bv[k], w[v][1], av[k] * w[v][0])));
+            s[v][k] = bilinear4(av[k], bv[k], cv[k], dv[k], w[v]);
         }
       }
     }
@@ -356,7 +308,7 @@ __global__ __launch_bounds__(kThreads) void unproject_bwd_tiled(
           // is: that rare case (a NaN or infinite input) flags the in-image taps directly
           if (__builtin_isfinite(coef[v])) {
             unsigned long long* q0 = &gq[slot[v] * G + k];
-            unsigned long long* q1 = &gq[(slot[v] + rpitch[v]) * G + k];
+            unsigned long long* q1 = &gq[(slot[v] + rg.pitch[v]) * G + k];
             atomicAdd(q0, to_fix(coef[v] * w[v][0], fsc[k]));
             atomicAdd(q0 + G, to_fix(coef[v] * w[v][1], fsc[k]));
             atomicAdd(q1, to_fix(coef[v] * w[v][2], fsc[k]));
@@ -372,7 +324,7 @@ __global__ __launch_bounds__(kThreads) void unproject_bwd_tiled(
           }
         } else {
           float* base0 = reinterpret_cast<float*>(&gacc[slot[v]]) + k;
-          float* base1 = reinterpret_cast<float*>(&gacc[slot[v] + rpitch[v]]) + k;
+          float* base1 = reinterpret_cast<float*>(&gacc[slot[v] + rg.pitch[v]]) + k;
           atomicAdd(base0, coef[v] * w[v][0]);
           atomicAdd(base0 + 4, coef[v] * w[v][1]);
           atomicAdd(base1, coef[v] * w[v][2]);
@@ -408,16 +360,10 @@ __global__ __launch_bounds__(kThreads) void unproject_bwd_tiled(
 
     // ---- flush the footprint: one global atomic per touched (pixel, channel) ---------
     for (int idx = t; idx < total; idx += kThreads) {
-      int v = 0;
-#pragma unroll
-      for (int u = 1; u < NV; ++u) if (u < N && idx >= rbase[u]) v = u;
-      int bwv = 0, pv = 1, xs = 0, ys = 0, base = 0;
-#pragma unroll
-      for (int u = 0; u < NV; ++u) if (u == v) { pv = rpitch[u]; bwv = rbw[u]; xs = rx[u]; ys = ry[u]; base = rbase[u]; }
-      const int py = (idx - base) / pv, px = idx - base - py * pv;
-      const int gx = xs + px, gy = ys + py;
-      if ((px < bwv) & (gx >= 0) & (gx < W) & (gy >= 0) & (gy < H)) {
-        const size_t pix = fbo + size_t(gy) * W + gx;
+      const SlotPixel p = slot_pixel(idx, 0, N, rg, H, W);
+      const int v = p.view;
+      if (p.in) {
+        const size_t pix = fbo + size_t(p.gy) * W + p.gx;
         if constexpr (DET) {
 #pragma unroll
           for (int k = 0; k < G; ++k) {

@@ -218,25 +218,6 @@ __device__ __forceinline__ void store_b128_padded(u32x4_t v, __amdgpu_buffer_rsr
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// Wave-wide integer min / max, returned wave-uniform.  row_shr DPP steps (identity
-// shifted in) leave each row's reduction in its lane 15; four readlanes combine the rows.
-__device__ __forceinline__ int wave_min_u(int v) {
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x111, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x112, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x114, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x118, 0xf, 0xf, false));
-  return min(min(__builtin_amdgcn_readlane(v, 15), __builtin_amdgcn_readlane(v, 31)),
-             min(__builtin_amdgcn_readlane(v, 47), __builtin_amdgcn_readlane(v, 63)));
-}
-__device__ __forceinline__ int wave_max_u(int v) {
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x111, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x112, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x114, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x118, 0xf, 0xf, false));
-  return max(max(__builtin_amdgcn_readlane(v, 15), __builtin_amdgcn_readlane(v, 31)),
-             max(__builtin_amdgcn_readlane(v, 47), __builtin_amdgcn_readlane(v, 63)));
-}
-
 // One voxel, all channels, taps gathered from global memory (oversize-footprint fallback).
 // Rolled loops and geometry recomputed per (channel, view): slow but register-lean, so
 // the staged path's register allocation is unaffected.  Same arithmetic and op order.

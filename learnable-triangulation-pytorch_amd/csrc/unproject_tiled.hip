@@ -1,4 +1,7 @@
-// Tiled, LDS-staged unprojection for gfx950 — the production kernel behind mvn_unproject.
+// Tiled, LDS-staged unprojection for gfx950 — the generic kernel for any N <= 8 views, channel
+// count and image width.  mvn_unproject runs it where the chunk-staged kernel (unproject_x4.hip)
+// does not apply, and the tests run it under the mvn_debug_set_unproject knob as the bit-exact
+// reference of that kernel.
 //
 // Same contract and numerics as the reference op (mvn/utils/op.py:99-163) and the simple
 // kernels in unproject.hip; what changes is where the bilinear taps come from.
@@ -29,15 +32,11 @@
 #include <climits>
 #include <utility>
 
-#include "unproject_common.hpp"
+#include "unproject_footprint.hpp"
 
 namespace mvn {
 namespace unproj {
 namespace {
-
-// 4 views: skip, per wave, staged slots past the tile's footprint (A/B r04: 194.2 -> 191.1 us
-// at config 2, bit-identical); 8 views stage every slot a thread owns (1,031 vs 1,061 us).
-
 
 // Tile of voxels per block (z fastest: a wave's output stores are 16-voxel = 64-byte runs
 // of a channel plane) and 16-byte LDS pixel slots per staging buffer (two per block; the
@@ -64,16 +63,9 @@ template <> __device__ __forceinline__ uint32_t buf_load<uint16_t>(__amdgpu_buff
   return __builtin_amdgcn_raw_buffer_load_b16(r, v, s, 0);
 }
 
-template <typename T> __device__ __forceinline__ void buf_store(float x, __amdgpu_buffer_rsrc_t r, uint32_t v, uint32_t s);
-// f32 planes non-temporal (A/B: 8 views, step 1,195 -> 1,179 us at 16 frames); XCD slabs from
-// 16 frames on
-constexpr int kTiledStorePolicyF32 = 2, kTiledXcdMinFrames = 16;
-template <> __device__ __forceinline__ void buf_store<float>(float x, __amdgpu_buffer_rsrc_t r, uint32_t v, uint32_t s) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), r, v, s, kTiledStorePolicyF32);
-}
-template <> __device__ __forceinline__ void buf_store<uint16_t>(float x, __amdgpu_buffer_rsrc_t r, uint32_t v, uint32_t s) {
-  __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, static_cast<__bf16>(x)), r, v, s, 0);
-}
+// Output planes go out through store_plane (unproject_common.hpp): f32 non-temporal (A/B: 8 views,
+// step 1,195 -> 1,179 us at 16 frames).  XCD slabs from 16 frames on.
+constexpr int kTiledXcdMinFrames = 16;
 
 // LDS slots (SlotT) hold G f32 channels whatever the input dtype (G = 4: 16-byte slots; G = 2:
 // 8-byte slots, half the LDS per block, so that two 8-view blocks share a CU): bf16 maps
@@ -91,25 +83,6 @@ template <typename TIn> __device__ __forceinline__ uint4 pack(const uint32_t (&b
 template <typename TIn> __device__ __forceinline__ uint2 pack(const uint32_t (&b)[2]) {
   if constexpr (sizeof(TIn) == 4) return make_uint2(b[0], b[1]);
   else return make_uint2(b[0] << 16, b[1] << 16);
-}
-
-// The LDS region (view) a staged slot index falls in, for one pass.  A select chain over
-// the views: indexing the per-view arrays with a per-lane view number would force them
-// into scratch memory.
-struct SlotRegion {
-  int v, x, y, bw, pitch, base;
-  float inv;
-};
-template <int NV>
-__device__ __forceinline__ SlotRegion find_region(int idx, int pass, int N, const int (&rx)[NV], const int (&ry)[NV],
-                                                  const int (&rbw)[NV], const int (&rpitch)[NV],
-                                                  const int (&rbase)[NV], const int (&rpass)[NV],
-                                                  const float (&rinv)[NV]) {
-  SlotRegion q{0, rx[0], ry[0], rbw[0], rpitch[0], rbase[0], rinv[0]};
-#pragma unroll
-  for (int u = 0; u < NV; ++u)
-    if (u < N && rpass[u] == pass && idx >= rbase[u]) q = SlotRegion{u, rx[u], ry[u], rbw[u], rpitch[u], rbase[u], rinv[u]};
-  return q;
 }
 
 // NV = views held in registers (4 or 8); EXACT: the launch has exactly NV views, so every
@@ -133,9 +106,7 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
 
   __shared__ Slot stage[2 * kBuf];
   __shared__ int red[kWaves][NV][4];
-  __shared__ int region[NV][6];                       // xs, ys, bw, pitch, first slot, end slot
-  __shared__ int region_pass[NV];
-  __shared__ float region_inv_pitch[NV];
+  __shared__ int region[NV][kRegionWordsPasses];
   __shared__ int block_info[2];                       // passes (-1: global fallback), slots of pass 0
 
   // ---- which tile (z-tiles fastest) -------------------------------------------------
@@ -182,9 +153,9 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
   }
 
   // ---- per-view geometry: footprint base pixel, weights, "samples the image" flag --
-  int fx[NV], fy[NV];
-  float w[NV][4];
-  bool has[NV];
+  int fx[NV] = {}, fy[NV] = {};
+  float w[NV][4] = {};
+  bool has[NV] = {};
   bool lane_fast = true;
 #pragma unroll
   for (int v = 0; v < NV; ++v)
@@ -194,22 +165,11 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
   const Recip rH = recip_refined(float(H)), rW = recip_refined(float(W));
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
-    has[v] = false;
-    fx[v] = fy[v] = 0;
-    w[v][0] = w[v][1] = w[v][2] = w[v][3] = 0.f;
     if (v < N) {
       const Homog hp = homog(Pb + v * 12, cx, cy, cz);
       const Proj p = (EXACT && wave_fast) ? project_h<true>(hp, H, W, align_corners, rH, rW)
                                           : project_h<false>(hp, H, W, align_corners, rH, rW);
-      const float fx0 = floorf(p.ix), fy0 = floorf(p.iy);
-      // at least one of the 4 taps lies inside the image, and the voxel is in front
-      const bool h = act & !p.invalid & (fx0 >= -1.f) & (fx0 < float(W)) & (fy0 >= -1.f) & (fy0 < float(H));
-      if (h) {
-        const float tx_ = p.ix - fx0, sx_ = 1.f - tx_, ty_ = p.iy - fy0, sy_ = 1.f - ty_;
-        w[v][0] = sy_ * sx_; w[v][1] = sy_ * tx_; w[v][2] = ty_ * sx_; w[v][3] = ty_ * tx_;
-        fx[v] = int(fx0); fy[v] = int(fy0);
-      }
-      has[v] = h;
+      has[v] = footprint_base(p, act, H, W, fx[v], fy[v], w[v]);
     }
   }
 
@@ -217,53 +177,12 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     if (v >= N) break;
-    const int x0 = wave_min_u(has[v] ? fx[v] : INT_MAX), x1 = wave_max_u(has[v] ? fx[v] : INT_MIN);
-    const int y0 = wave_min_u(has[v] ? fy[v] : INT_MAX), y1 = wave_max_u(has[v] ? fy[v] : INT_MIN);
-    if (lane == 0) { red[wid][v][0] = x0; red[wid][v][1] = x1; red[wid][v][2] = y0; red[wid][v][3] = y1; }
+    wave_box(has[v], fx[v], fy[v], lane, red[wid][v]);
   }
   __syncthreads();
-  if (t == 0) {
-    int next = 0, pass = 0, slots0 = 0;
-    bool too_big = false;
-    budget = min(budget, kZeroSlot);
-    for (int v = 0; v < NV; ++v) {
-      if (v >= N) break;
-      int x0 = INT_MAX, x1 = INT_MIN, y0 = INT_MAX, y1 = INT_MIN;
-      for (int q = 0; q < kWaves; ++q) {
-        x0 = min(x0, red[q][v][0]); x1 = max(x1, red[q][v][1]);
-        y0 = min(y0, red[q][v][2]); y1 = max(y1, red[q][v][3]);
-      }
-      int bw = 0, bh = 0;
-      if (x0 <= x1) { bw = x1 - x0 + 2; bh = y1 - y0 + 2; }   // +1 px for the east / south taps
-      const int pitch = bw | 1;                                 // odd: spreads rows over banks
-      const long long area = (long long)pitch * bh;
-      if (area > budget) too_big = true;
-      if (next + area > budget) { ++pass; next = 0; }
-      region[v][0] = x0; region[v][1] = y0; region[v][2] = bw; region[v][3] = pitch;
-      region[v][4] = next; region[v][5] = next + int(area);
-      region_pass[v] = pass;
-      region_inv_pitch[v] = 1.f / float(pitch);
-      next += int(area);
-      if (pass == 0) slots0 = next;
-    }
-    block_info[0] = too_big ? -1 : pass + 1;
-    block_info[1] = slots0;
-  }
+  if (t == 0) layout_regions(red, region, block_info, N, min(budget, kZeroSlot), INT_MAX);
   __syncthreads();
-
-  int rx[NV], ry[NV], rbw[NV], rpitch[NV], rbase[NV], rend[NV], rpass[NV];
-  float rinv[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {       // block-uniform: keep in SGPRs
-    rx[v] = __builtin_amdgcn_readfirstlane(region[v][0]);
-    ry[v] = __builtin_amdgcn_readfirstlane(region[v][1]);
-    rbw[v] = __builtin_amdgcn_readfirstlane(region[v][2]);
-    rpitch[v] = __builtin_amdgcn_readfirstlane(region[v][3]);
-    rbase[v] = __builtin_amdgcn_readfirstlane(region[v][4]);
-    rend[v] = __builtin_amdgcn_readfirstlane(region[v][5]);
-    rpass[v] = __builtin_amdgcn_readfirstlane(region_pass[v]);
-    rinv[v] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(region_inv_pitch[v])));
-  }
+  const auto rg = load_regions(region);
   const int npass = __builtin_amdgcn_readfirstlane(block_info[0]);
 
   if (npass < 0) {
@@ -283,9 +202,9 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
   uint32_t anw[NV], asw[NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
-    const int slot = rbase[v] + (fy[v] - ry[v]) * rpitch[v] + (fx[v] - rx[v]);
-    anw[v] = uint32_t(has[v] ? slot : kZeroSlot) * kSlotB;
-    asw[v] = uint32_t(has[v] ? slot + rpitch[v] : kZeroSlot) * kSlotB;
+    const int nw = tap_slot(has[v], fx[v], fy[v], rg.x[v], rg.y[v], rg.pitch[v], rg.base[v], kZeroSlot);
+    anw[v] = uint32_t(nw) * kSlotB;
+    asw[v] = uint32_t(has[v] ? nw + rg.pitch[v] : kZeroSlot) * kSlotB;
   }
 
   // sample the views staged in an LDS buffer (ONE_PASS: all of them; else those of `pass`)
@@ -293,7 +212,7 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       if (v >= N) continue;
-      if (!decltype(one_pass)::value && rpass[v] != pass) continue;
+      if (!decltype(one_pass)::value && rg.pass[v] != pass) continue;
       // branch-free: voxel-views that sample nothing read the zero slots with zero weights
       float a[G], bq[G], cq[G], d[G];
       unpack(*reinterpret_cast<const Slot*>(buf + anw[v]), a);
@@ -302,8 +221,7 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
       unpack(*reinterpret_cast<const Slot*>(buf + asw[v] + kSlotB), d);
 #pragma unroll
       for (int ch = 0; ch < G; ++ch)
-        sv[ch][v] = __builtin_fmaf(d[ch], w[v][3], __builtin_fmaf(cq[ch], w[v][2],
-                    __builtin_fmaf(bq[ch], w[v][1], a[ch] * w[v][0])));
+        sv[ch][v] = bilinear4(a[ch], bq[ch], cq[ch], d[ch], w[v]);
       if (v & 1) __builtin_amdgcn_sched_barrier(0);   // at most two views' taps in flight
     }
   };
@@ -343,7 +261,7 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
       const int c = c0 + ch;
       if (c >= C) break;
       const uint32_t soff = uint32_t(c) * uint32_t(nvox) * uint32_t(sizeof(TOut));
-      buf_store<TOut>(aggregate<AGG, NV>(sv[ch], N, cfb ? cfb + c : nullptr, C), ors, ooff, soff);
+      store_plane<TOut>(aggregate<AGG, NV>(sv[ch], N, cfb ? cfb + c : nullptr, C), ors, ooff, soff);
     }
   };
 
@@ -358,13 +276,8 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
 #pragma unroll
     for (int i = 0; i < MS; ++i) {
       const int idx = t + kThreads * i;
-      const SlotRegion q = find_region<NV>(idx, 0, N, rx, ry, rbw, rpitch, rbase, rpass, rinv);
-      const int li = idx - q.base;
-      const int py = int((float(li) + 0.5f) * q.inv);
-      const int px = li - py * q.pitch;
-      const int gx = q.x + px, gy = q.y + py;
-      const bool in = (idx < total) & (px < q.bw) & (gx >= 0) & (gx < W) & (gy >= 0) & (gy < H);
-      goff[i] = in ? uint32_t((q.v * C * HW + gy * W + gx) * int(sizeof(TIn))) : kOob;
+      const SlotPixel q = slot_pixel(idx, 0, N, rg, H, W);
+      goff[i] = ((idx < total) & (q.in != 0)) ? uint32_t((q.view * C * HW + q.gy * W + q.gx) * int(sizeof(TIn))) : kOob;
     }
     uint32_t pre[MS][G];
     constexpr bool UNCOND = NV == 8;
@@ -413,9 +326,11 @@ __attribute__((amdgpu_waves_per_eu(TileShape<NV>::WAVES))) void unproject_tiled(
     for (int pass = 0; pass < npass; ++pass) {
       int total = 0;
 #pragma unroll
-      for (int v = 0; v < NV; ++v) if (v < N && rpass[v] == pass) total = max(total, rend[v]);
+      for (int v = 0; v < NV; ++v) if (v < N && rg.pass[v] == pass) total = max(total, rg.end[v]);
       for (int idx = t; idx < total; idx += kThreads) {
-        const SlotRegion q = find_region<NV>(idx, pass, N, rx, ry, rbw, rpitch, rbase, rpass, rinv);
+        // slot_pixel written out: as a function it is simplified before it is inlined and this
+        // loop comes out 2-4 instructions longer (idx - base formed again at each use)
+        const SlotRegion q = slot_region<NV>(idx, pass, N, rg);
         const int li = idx - q.base;
         const int py = int((float(li) + 0.5f) * q.inv);
         const int px = li - py * q.pitch;

@@ -104,6 +104,60 @@ template <> struct X4Shape<5> {
   static constexpr int STORE_F32 = kStorePolicyF32;
 };
 
+// Per buffer: image slots [0, kX4Trash), 64 per-lane trash slots, 2 zero slots (the taps of
+// voxel-views that sample nothing point there).
+template <int K> constexpr int kX4Trash = X4Shape<K>::SLOTS - 2 - kWave;
+
+// Which shape a call gets: views, bf16 or f32 maps, f32 or bf16 output, channels-last output,
+// fast arithmetic, and `wide` (the test knob that asks for shape 0 where 5 would run).  -1: not
+// this kernel's call.
+//   8 views                          3   (NCDHW only)
+//   4 views, bf16 maps               4 when fast and NCDHW (r21), else 2
+//   4 views, f32 maps                5 when exact, NCDHW, f32 output and not `wide` (r24), else 0
+constexpr int x4_shape_of(int views, bool bf16_maps, bool f32_out, bool cl, bool fast, bool wide) {
+  if (views == 8) return cl ? -1 : 3;
+  if (views != 4) return -1;
+  if (bf16_maps) return fast && !cl ? 4 : 2;
+  return f32_out && !cl && !fast && !wide ? 5 : 0;
+}
+// whether some call selects (K, CL, FAST) for these dtypes: only such kernels are instantiated
+constexpr bool x4_reachable(int K, bool bf16_maps, bool f32_out, bool cl, bool fast) {
+  return K == x4_shape_of(8, bf16_maps, f32_out, cl, fast, false) || K == x4_shape_of(4, bf16_maps, f32_out, cl, fast, false) ||
+         K == x4_shape_of(4, bf16_maps, f32_out, cl, fast, true);
+}
+
+// The decisions of one instantiation, each an A/B result about its shape.
+template <int K, typename TIn, int CL, int FAST, int AGG>
+struct X4Policy {
+  using S = X4Shape<K>;
+  // bf16 pixel-pair slots (fast, bf16 maps, 16-byte slots) — dword k of the slot at pixel (x, y)
+  // holds channel k's (x, x+1) bf16 pair, so a voxel-view reads 2 slots (rows y0, y1) per 4
+  // channels instead of 4, and each row is one v_dot2_f32_bf16 against the (west, east) bf16
+  // weight pair.  A slot needs pixel x+4 of its chunk's right neighbour: chunks are dealt to a
+  // wave's lanes 63 at a time, lane 63 loading the next wave's first chunk only to hand it to
+  // lane 62 (DPP wave_shl:1) and writing nothing.
+  static constexpr bool kPairSlots = FAST != 0 && sizeof(TIn) == 2 && S::G == 4;
+  // fast softmax: the samples carry a log2(e) factor and the max pass is skipped
+  static constexpr bool kLog2Softmax = FAST != 0 && AGG == MVN_AGG_SOFTMAX;
+  // ... its range guard once per voxel after the channel loop; else per group (8 views: at the
+  // register limit of 3 waves per SIMD the loop-carried range spills; f32 channels-last: spills)
+  static constexpr bool kDeferredGuard = S::NV == 4 && (sizeof(TIn) == 2 || CL == 0);
+  // 4 views on 2-channel slots (shape 5): the weight pairs broadcast by op_sel (r24)
+  static constexpr bool kSelWeights = S::NV == 4 && S::G == 2;
+  // fast, and every shape at 6 waves per SIMD: the tap offsets before the staging starts, so that
+  // the per-view base pixels die there (live into the multi-pass branch they spilled at 6 waves)
+  static constexpr bool kTapsFirst = FAST != 0 || S::WAVES == 6;
+  // masked-off pixels of a chunk: bf16 maps and the 8-view 2-channel slots write them to the
+  // lane's trash slot (no exec-mask branch per write), f32 maps at 4 views branch (A/B at the
+  // bench configs: each is the faster for its case; 8 views 694 -> 677 us, r16; shape 5
+  // 143.9 -> 136.6 us, r24)
+  static constexpr bool kTrashWrites = sizeof(TIn) == 2 || (S::G == 2 && S::NV == 8);
+  // 8-byte slots are read as single ds_read_b64 (2 LDS cycles, 64 banks): left to itself the
+  // compiler pairs the two taps of a row into ds_read2_b64, which the LDS services as two
+  // 16-lane-group accesses at half the rate (8 cycles, 32 banks) — config 4: 774 -> 694 us (r16)
+  static constexpr bool kUnpairedTapReads = S::G == 2;
+};
+
 // channel pair q of a slot (SlotT<G>: one pixel's G channels as f32)
 __device__ __forceinline__ f2 slot_pair(const uint4& s, int q) { return q ? hi2(s) : lo2(s); }
 __device__ __forceinline__ f2 slot_pair(const uint2& s, int) { return f2{__uint_as_float(s.x), __uint_as_float(s.y)}; }
@@ -164,6 +218,9 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
     const float* __restrict__ cub, int transfer, const float* __restrict__ conf, TOut* __restrict__ out, int B,
     int C, int H, int W, int Vx, int Vy, int Vz, int align_corners, int budget) {
   using S = X4Shape<K>;
+  using Pol = X4Policy<K, TIn, CL, FAST, AGG>;
+  static_assert(x4_reachable(K, sizeof(TIn) == 2, sizeof(TOut) == 4, CL != 0, FAST != 0),
+                "no call selects this (shape, dtypes, layout, precision): see x4_shape_of");
   constexpr bool out_cl = CL != 0;
   constexpr int NV = S::NV, G = S::G, NP = G / 2;      // NP channel pairs per group
   constexpr int TX = S::TX, TY = S::TY, TZ = S::TZ;
@@ -171,19 +228,9 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
   static_assert(TX * TY * TZ == kThreads, "one voxel per thread");
   // validated tiles: TX 4 or 8, TY 8, TZ 8 or 16 (an 8x4x16 variant was not bit-identical, r21)
   static_assert(TY == 8 && (TX == 4 || TX == 8), "tile shape outside the validated set");
-  // PAIR: bf16 pixel-pair slots — dword k of the slot at pixel (x, y) holds channel k's
-  // (x, x+1) bf16 pair, so a voxel-view reads 2 slots (rows y0, y1) per 4 channels instead of
-  // 4, and each row is one v_dot2_f32_bf16 against the (west, east) bf16 weight pair.  A
-  // slot needs pixel x+4 of its chunk's right neighbour: chunks are dealt to a wave's lanes
-  // 63 at a time, lane 63 loading the next wave's first chunk only to hand it to lane 62
-  // (DPP wave_shl:1) and writing nothing.
-  constexpr bool PAIR = FAST != 0 && sizeof(TIn) == 2 && G == 4;
-  constexpr bool SMXF = FAST != 0 && AGG == MVN_AGG_SOFTMAX;   // samples carry a log2(e) factor
-  constexpr int kLanesW = PAIR ? kWave - 1 : kWave;               // chunks a wave owns per slot i
+  constexpr int kLanesW = Pol::kPairSlots ? kWave - 1 : kWave;               // chunks a wave owns per slot i
   constexpr int kCap = MC * kWaves * kLanesW;                       // chunk capacity of one pass
-  // per buffer: image slots [0, kTrash), 64 per-lane trash slots (the masked-off pixels of
-  // a chunk are written there: no exec-mask branch per write), 2 zero slots
-  constexpr int kZeroSlot = kBuf - 2, kTrash = kBuf - 2 - kWave;
+  constexpr int kZeroSlot = kBuf - 2, kTrash = kX4Trash<K>;
   static_assert(kBuf <= (1 << 13) && kCap < (1 << 11), "RegionSet packs sbase in 13 bits and cbase in 11");
   // LDS slot = one pixel's G channels as f32 (16 / 8 bytes; bf16 maps are widened exactly
   // when staged: bf16 slots halve the LDS bytes but the per-tap widening costs more VALU, r13)
@@ -247,7 +294,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
   }
   int fx[NV], fy[NV];
   f2 wp[NV][2];                        // bilinear weights (nw, ne), (sw, se) per view
-  uint32_t wq[NV][2];                  // PAIR: the same as bf16 pairs (nw | ne << 16), (sw | se << 16)
+  uint32_t wq[NV][2];                  // pair slots: the same as bf16 pairs (nw | ne << 16), (sw | se << 16)
   bool has[NV];
   // per-voxel geometry: footprint base pixel, bilinear weights, "samples the image" flag
   auto project_voxel = [&]() __attribute__((always_inline)) {
@@ -260,7 +307,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
       const float ay = (align_corners ? fH - 1.f : fH) * __builtin_amdgcn_rcpf(fW);
       const float bo = align_corners ? 0.f : -0.5f;
       // softmax: the weights carry log2(e), so each sample is s * log2(e) (aggregate below)
-      const float ks = SMXF ? kLog2e : 1.f;
+      const float ks = Pol::kLog2Softmax ? kLog2e : 1.f;
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
         const Homog hp = homog(Pb + v * 12, cx, cy, cz);
@@ -271,7 +318,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
         const float tx_ = ix - fx0, sx_ = 1.f - tx_, ty_ = (iy - fy0) * ks, sy_ = ks - ty_;
         wp[v][0] = f2{h ? sy_ * sx_ : 0.f, h ? sy_ * tx_ : 0.f};
         wp[v][1] = f2{h ? ty_ * sx_ : 0.f, h ? ty_ * tx_ : 0.f};
-        if constexpr (PAIR) {
+        if constexpr (Pol::kPairSlots) {
           wq[v][0] = pack_bf16x2(wp[v][0].x, wp[v][0].y);
           wq[v][1] = pack_bf16x2(wp[v][1].x, wp[v][1].y);
         }
@@ -425,7 +472,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
   };
   // Chunk (k of a pass) -> global byte offset (kOob outside the image), first LDS slot and
   // the mask of its 4 pixels that lie in the view's box (empty past the pass's chunks).
-  const bool writer = !PAIR || lane != kWave - 1;      // PAIR: lane 63 only feeds lane 62
+  const bool writer = !Pol::kPairSlots || lane != kWave - 1;      // pair slots: lane 63 only feeds lane 62
   auto chunk_fields = [&](const Region& r, int sel, int li, uint32_t& goff, int& s0, uint32_t& mask, bool live)
       __attribute__((always_inline)) {
     // li = row * cw + chunk column (rows fastest-varying outer)
@@ -435,8 +482,8 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
     goff = in ? uint32_t((sel * C * HW + gy * W + gx) * int(E)) : kOob;
     s0 = r.sbase + py * r.pitch + (gx - r.x0);
     mask = 0;
-    // PAIR: the slot of pixel dx holds (dx, dx+1): the box's last column is never a base
-    const int xend = PAIR ? r.bw - 1 : r.bw;
+    // pair slots: the slot of pixel dx holds (dx, dx+1): the box's last column is never a base
+    const int xend = Pol::kPairSlots ? r.bw - 1 : r.bw;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int dx = gx + p - r.x0;
@@ -448,11 +495,9 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
 #pragma unroll
     for (int k = 0; k < G; ++k) pre[k] = load_chunk<TIn>(frs, goff, uint32_t((c0 + k) * HW) * E);
   };
-  // masked-off pixels: bf16 maps and the 8-view 2-channel slots write them to the lane's trash
-  // slot (no exec-mask branch per write), f32 maps at 4 views branch (A/B at the bench configs:
-  // each is the faster for its case; 8 views 694 -> 677 us, r16; X4Shape<5> 143.9 -> 136.6 us, r24)
+  // masked-off pixels go to the lane's trash slot or are branched over (Pol::kTrashWrites)
   auto write_group = [&](Slot* buf, const Chunk (&pre)[G], int s0, uint32_t mask) __attribute__((always_inline)) {
-    if constexpr (PAIR) {
+    if constexpr (Pol::kPairSlots) {
       // chunk dwords: lo = (px0, px1), hi = (px2, px3) of one channel; pixels 4, 5 are the
       // right neighbour lane's lo.  Slot p, dword k: channel k's (px p, px p+1).
       uint32_t nb[G];
@@ -478,20 +523,17 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
       else
         q = make_uint2(chunk_px(pre[0], p), chunk_px(pre[1], p));
       MVN_DASSERT(!(mask & (1u << p)) || (s0 + p >= 0 && s0 + p < kTrash));   // a box slot, not trash / zero
-      if constexpr (sizeof(TIn) == 2 || (G == 2 && NV == 8))
+      if constexpr (Pol::kTrashWrites)
         buf[(mask & (1u << p)) ? s0 + p : kTrash + lane] = q;
       else if (mask & (1u << p))
         buf[s0 + p] = q;
     }
   };
 
-  // one tap's slot.  8-byte slots are read as single ds_read_b64 (2 LDS cycles, 64 banks):
-  // left to itself the compiler pairs the two taps of a row into ds_read2_b64, which the
-  // LDS services as two 16-lane-group accesses at half the rate (8 cycles, 32 banks) —
-  // config 4: 774 -> 694 us (r16).  A volatile LDS load is not merged; its order relative
-  // to the other taps is the program order anyway.
+  // one tap's slot.  Pol::kUnpairedTapReads: a volatile LDS load is not merged with its
+  // neighbour; its order relative to the other taps is the program order anyway.
   auto tap = [&](const char* p) __attribute__((always_inline)) -> Slot {
-    if constexpr (sizeof(Slot) == 8) {
+    if constexpr (Pol::kUnpairedTapReads) {
       typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
       typedef const volatile __attribute__((address_space(3))) u32x2* lds_ptr;
       const u32x2 q = *(lds_ptr)(p);
@@ -500,14 +542,12 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
       return *reinterpret_cast<const Slot*>(p);
     }
   };
-  // 4 views on 2-channel slots (X4Shape<5>): the weight pairs broadcast by op_sel
-  constexpr bool kSelWeights = NV == 4 && G == 2;
   // sample the views staged in an LDS buffer (all, or those of `pass`) into channel pairs
   auto sample_views = [&](const char* buf, bool all, int pass, f2 (&sv)[NP][NV]) __attribute__((always_inline)) {
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       if (!all && rs.get(v).pass != pass) continue;
-      if constexpr (PAIR) {
+      if constexpr (Pol::kPairSlots) {
         // two slots per view (rows y0, y1), one v_dot2_f32_bf16 per row and channel
         const Slot a = tap(buf + anw[v]);
         const Slot cq = tap(buf + asw[v]);
@@ -529,7 +569,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
       const Slot bq = tap(buf + anw[v] + kSlotB);
       const Slot cq = tap(buf + asw[v]);
       const Slot d = tap(buf + asw[v] + kSlotB);
-      if constexpr (kSelWeights) {
+      if constexpr (Pol::kSelWeights) {
         sv[0][v] = pk_fma_sel<1>(slot_pair(d, 0), wp[v][1],
                                  pk_fma_sel<0>(slot_pair(cq, 0), wp[v][1],
                                                pk_fma_sel<1>(slot_pair(bq, 0), wp[v][0], pk_mul_sel<0>(slot_pair(a, 0), wp[v][0]))));
@@ -544,14 +584,13 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
       if (v & 1) __builtin_amdgcn_sched_barrier(0);   // at most two views' taps in flight
     }
   };
-  // SMXF: range of the max-free softmax's denominators over every channel of this voxel.
+  // Pol::kLog2Softmax: range of the max-free softmax's denominators over every channel of this voxel.
   // Outside [2^-100, 2^120] (|s| beyond ~70: overflow, or underflow in every view) the wave
   // recomputes its voxels with the exact gather path after the channel loop (rare; NaNs do
   // not trip it — a NaN sample gives a NaN value in either form, as in the reference).
-  constexpr bool kDeferredGuard = NV == 4 && (sizeof(TIn) == 2 || CL == 0);   // (f32 channels-last: spills)
   float dmx = 0.f, dmn = INFINITY;
   auto range_fallback = [&]() __attribute__((always_inline)) {
-    if constexpr (SMXF && kDeferredGuard) {
+    if constexpr (Pol::kLog2Softmax && Pol::kDeferredGuard) {
       if (__builtin_amdgcn_ballot_w64(!(dmx <= 0x1p120f) || !(dmn >= 0x1p-100f))) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the fast values' stores land first
         // the voxel's coordinates formed again from its index (opaque to the compiler, so that
@@ -576,17 +615,16 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
 #pragma unroll
   for (int k = 0; k < NG - 1; ++k) cl_buf[k] = make_uint2(0u, 0u);
   auto aggregate = [&](int c0, const f2 (&sv)[NP][NV], float (&r)[G]) __attribute__((always_inline)) {
-    if constexpr (SMXF) {
+    if constexpr (Pol::kLog2Softmax) {
       // max-free softmax of the log2-scaled samples; the denominators' range is tracked over
-      // all groups and checked once per voxel at the end (range_fallback).  8 views: at the
-      // register limit of 3 waves per SIMD the loop-carried range spills, so the group checks
-      // its own range and redoes itself max-first.
+      // all groups and checked once per voxel at the end (range_fallback), or the group checks
+      // its own range and redoes itself max-first (Pol::kDeferredGuard).
       float gmx = 0.f, gmn = INFINITY;
 #pragma unroll
       for (int q = 0; q < NP; ++q) {
         f2 den;
         const f2 o = softmax_pair_log2<NV, false>(sv[q], den);
-        if constexpr (kDeferredGuard) {
+        if constexpr (Pol::kDeferredGuard) {
           dmx = vmax3f(dmx, den.x, den.y);
           dmn = vmin3f(dmn, den.x, den.y);
         } else {
@@ -596,7 +634,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
         r[2 * q] = o.x;
         r[2 * q + 1] = o.y;
       }
-      if constexpr (!kDeferredGuard) {
+      if constexpr (!Pol::kDeferredGuard) {
         if (__builtin_amdgcn_ballot_w64(!(gmx <= 0x1p120f) || !(gmn >= 0x1p-100f))) {
 #pragma unroll
           for (int q = 0; q < NP; ++q) {
@@ -625,7 +663,8 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
   // record (config 5).  bf16 NCDHW planes are direct 2-byte stores (r14: once the stores were
   // deferred past the next commit they beat 16-byte rows gathered through LDS, 542 -> 530 us).
   auto store_out = [&](int c0, const float (&r)[G]) __attribute__((always_inline)) {
-    if constexpr (G == 4 && CL != 0) {      // (launch_x4 sends channels-last 8-view calls to the tiled kernel)
+    if constexpr (out_cl) {
+      static_assert(G == 4, "channels-last records are written from 16-byte slots");
       // c0 is block-uniform; readfirstlane keeps it scalar (soffset operands must be SGPRs)
       const uint32_t soff = __builtin_amdgcn_readfirstlane(uint32_t(c0) * uint32_t(sizeof(TOut)));
       if constexpr (sizeof(TOut) == 2) {
@@ -676,10 +715,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // fast, and every shape at 6 waves per SIMD: the tap offsets before the staging starts, so that
-  // the per-view base pixels die here (live into the multi-pass branch they spilled at 6 waves)
-  constexpr bool kTapsFirst = FAST != 0 || S::WAVES == 6;
-  if constexpr (kTapsFirst) tap_slots();
+  if constexpr (Pol::kTapsFirst) tap_slots();
   if (npass == 1) {
     // ---- one pass: up to MC chunks per thread (chunk t + kThreads * i over the views'
     // concatenated chunk ranges), two LDS buffers, the next group's loads in flight --------
@@ -687,7 +723,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
     int s0[MC];
 #pragma unroll
     for (int i = 0; i < MC; ++i) {
-      const int k = i * kWaves * kLanesW + wid * kLanesW + lane;     // = t + kThreads * i unless PAIR
+      const int k = i * kWaves * kLanesW + wid * kLanesW + lane;     // = t + kThreads * i unless pair slots
       int sel = 0;
 #pragma unroll
       for (int u = 1; u < NV; ++u)
@@ -708,7 +744,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
         if (wfirst + kWaves * kLanesW * i < total) write_group(buf, pre[i], s0[i], mask[i]);
     };
     issue(0);
-    if constexpr (!kTapsFirst) tap_slots();
+    if constexpr (!Pol::kTapsFirst) tap_slots();
     commit(stageA);
     __syncthreads();
     // A group's outputs are stored after the NEXT group's commit: on gfx950 vmcnt counts
@@ -737,7 +773,7 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
   }
 
   // ---- several passes of whole views per channel group (close cameras) ---------------
-  if constexpr (!kTapsFirst) tap_slots();
+  if constexpr (!Pol::kTapsFirst) tap_slots();
   for (int c0 = 0; c0 < C; c0 += G) {
     f2 sv[NP][NV];
     for (int pass = 0; pass < npass; ++pass) {
@@ -768,79 +804,66 @@ __global__ __launch_bounds__(X4Shape<K>::THREADS) __attribute__((amdgpu_waves_pe
 
 }  // namespace
 
+// Launches the instantiation (K, CL, FAST) = I-th of 5 shapes x 2 layouts x 2 precisions that the call
+// selected; only what x4_shape_of can select is instantiated (the kernel asserts the same).
+template <int AGG, typename TIn, typename TOut, int I = 0>
+int launch_x4_as(const UnprojCall& c, int shape, int budget) {
+  constexpr int kShapes[5] = {0, 2, 3, 4, 5};
+  constexpr int K = kShapes[I / 4], CL = I / 2 % 2, FAST = I % 2;
+  if constexpr (x4_reachable(K, sizeof(TIn) == 2, sizeof(TOut) == 4, CL != 0, FAST != 0)) {
+    if (shape == K && (c.out_cl != 0) == (CL != 0) && (c.fast != 0) == (FAST != 0)) {
+      using S = X4Shape<K>;
+      const long long nb = tile_blocks(c.B, c.Vx, c.Vy, c.Vz, S::TX, S::TY, S::TZ);
+      if (nb > INT_MAX) return MVN_ERR_SHAPE;
+      unproject_x4<AGG, TIn, TOut, K, CL, FAST><<<int(nb), S::THREADS, 0, c.s>>>(
+          static_cast<const TIn*>(c.feat), c.P, c.coords, c.cub, c.transfer, c.conf, static_cast<TOut*>(c.out), c.B,
+          c.C, c.H, c.W, c.Vx, c.Vy, c.Vz, c.align_corners, budget);
+      return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
+    }
+  }
+  if constexpr (I + 1 < 20) return launch_x4_as<AGG, TIn, TOut, I + 1>(c, shape, budget);
+  return 1;
+}
+
 // Returns MVN_OK, an error code, or 1 when this kernel does not apply (the caller then
 // runs unproject_tiled).
 template <int AGG, typename TIn, typename TOut>
 int launch_x4(const UnprojCall& c) {
   if (c.H > 32000 || c.W > 32000 || c.W % 4 != 0) return 1;
-  // 4 views: tile per input dtype (A/B at the bench configs), f32 4x8x16,
-  // bf16 8x8x8; 8 views: 2-channel slots, NCDHW output only
-  const bool four = c.N == 4 && c.C % 4 == 0, eight = c.N == 8 && c.C % 2 == 0 && !c.out_cl;
-  if (!four && !eight) return 1;
+  if (c.C % (c.N == 4 ? 4 : 2) != 0) return 1;
+  const int shape = x4_shape_of(c.N, sizeof(TIn) == 2, sizeof(TOut) == 4, c.out_cl != 0, c.fast != 0, unproject_force_wide_slots());
+  if (shape < 0) return 1;
   if (!frame_fits_32bit<TIn, TOut>(c)) return MVN_ERR_SHAPE;
-  const int budget = lds_slot_budget();
-  auto launch = [&](auto shape, auto cl, auto fast) {
-    constexpr int K = decltype(shape)::value, CL = decltype(cl)::value, FAST = decltype(fast)::value;
-    using S = X4Shape<K>;
-    const long long nb = tile_blocks(c.B, c.Vx, c.Vy, c.Vz, S::TX, S::TY, S::TZ);
-    if (nb > INT_MAX) return MVN_ERR_SHAPE;
-    unproject_x4<AGG, TIn, TOut, K, CL, FAST><<<int(nb), S::THREADS, 0, c.s>>>(
-        static_cast<const TIn*>(c.feat), c.P, c.coords, c.cub, c.transfer, c.conf, static_cast<TOut*>(c.out), c.B,
-        c.C, c.H, c.W, c.Vx, c.Vy, c.Vz, c.align_corners, budget);
-    return launch_ok() ? MVN_OK : MVN_ERR_LAUNCH;
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  auto go = [&](auto shape, auto cl) {
-    constexpr int K = decltype(shape)::value, CL = decltype(cl)::value;
-    // bf16 maps, NCDHW, fast arithmetic: the 8x8x8 tile at 6 waves per SIMD (X4Shape<4>)
-    if constexpr (K == 2 && CL == 0)
-      if (c.fast) return launch(std::integral_constant<int, 4>{}, cl, I1{});
-    return c.fast ? launch(shape, cl, I1{}) : launch(shape, cl, I0{});
-  };
-  if (eight) return go(std::integral_constant<int, 3>{}, I0{});
-  using K4 = std::integral_constant<int, sizeof(TIn) == 2 ? 2 : 0>;
-  // f32 maps, NCDHW, exact arithmetic: 2-channel slots at 6 waves per SIMD (X4Shape<5>), unless
-  // the test knob asks for the 16-byte slots
-  if constexpr (sizeof(TIn) == 4 && sizeof(TOut) == 4)
-    if (!c.out_cl && !c.fast && !unproject_force_wide_slots()) return launch(std::integral_constant<int, 5>{}, I0{}, I0{});
-  return c.out_cl ? go(K4{}, I1{}) : go(K4{}, I0{});
+  return launch_x4_as<AGG, TIn, TOut>(c, shape, lds_slot_budget());
 }
 
-// Diagnostics (mvn_debug_unproject_occupancy): resident blocks per CU of the softmax kernels.
-int x4_blocks_per_cu(int bf16) {
+// Resident blocks per CU of a kernel launched with `threads`; its private-segment bytes and registers.
+template <typename Kernel>
+int x4_occupancy(Kernel kernel, int threads, int* private_bytes, int* registers) {
   int n = 0;
-  const hipError_t e =
-      bf16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, unproject_x4<MVN_AGG_SOFTMAX, uint16_t, uint16_t, 2, 0, 0>,
-                                                          X4Shape<2>::THREADS, 0)
-           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, unproject_x4<MVN_AGG_SOFTMAX, float, float, 0, 0, 0>,
-                                                          X4Shape<0>::THREADS, 0);
-  return e == hipSuccess ? n : MVN_ERR_LAUNCH;
+  hipFuncAttributes a;
+  if (hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel)) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0) != hipSuccess)
+    return MVN_ERR_LAUNCH;
+  *private_bytes = int(a.localSizeBytes);
+  *registers = a.numRegs;
+  return n;
 }
-
-// mvn_debug_x4_shape_occupancy: the same for the f32 softmax kernel of X4Shape<0> or <5>, with the
-// kernel's private-segment bytes and register count
+// Diagnostics (mvn_debug_unproject_occupancy, mvn_debug_x4_shape_occupancy): the softmax kernels of
+// bf16 maps (X4Shape<2>) and of f32 maps on 16-byte (<0>) or 8-byte (<5>) slots
+int x4_blocks_per_cu(int bf16) {
+  int p, r;
+  return bf16 ? x4_occupancy(unproject_x4<MVN_AGG_SOFTMAX, uint16_t, uint16_t, 2, 0, 0>, X4Shape<2>::THREADS, &p, &r)
+              : x4_shape_occupancy(0, &p, &r);
+}
 int x4_shape_occupancy(int shape, int* private_bytes, int* registers) {
-  auto query = [&](auto kernel, int threads) {
-    int n = 0;
-    hipFuncAttributes a;
-    if (hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel)) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0) != hipSuccess)
-      return int(MVN_ERR_LAUNCH);
-    *private_bytes = int(a.localSizeBytes);
-    *registers = a.numRegs;
-    return n;
-  };
-  return shape == 5 ? query(unproject_x4<MVN_AGG_SOFTMAX, float, float, 5, 0, 0>, X4Shape<5>::THREADS)
-                    : query(unproject_x4<MVN_AGG_SOFTMAX, float, float, 0, 0, 0>, X4Shape<0>::THREADS);
+  return shape == 5 ? x4_occupancy(unproject_x4<MVN_AGG_SOFTMAX, float, float, 5, 0, 0>, X4Shape<5>::THREADS, private_bytes, registers)
+                    : x4_occupancy(unproject_x4<MVN_AGG_SOFTMAX, float, float, 0, 0, 0>, X4Shape<0>::THREADS, private_bytes, registers);
 }
 
 int x4_launch_order() { return kX4Order; }
-// kTrash of the kernel: a buffer's slots less the 64 trash and 2 zero slots
-int x4_image_slots(int shape) {
-  const int slots = shape == 0 ? X4Shape<0>::SLOTS : shape == 1 ? X4Shape<2>::SLOTS : X4Shape<3>::SLOTS;
-  return slots - 2 - kWave;
-}
+// the image slots of the f32 (0: X4Shape<0>), bf16 (1: <2>) and 8-view (2: <3>) shape
+int x4_image_slots(int shape) { return shape == 0 ? kX4Trash<0> : shape == 1 ? kX4Trash<2> : kX4Trash<3>; }
 
 #define MVN_INSTANTIATE(AGG)                                         \
   template int launch_x4<AGG, float, float>(const UnprojCall&);       \
