@@ -47,6 +47,9 @@
  *                           + BatchNorm2d + ReLU of the backbone's deconv head; eval mode)
  *   mvn_deconv4s2_project  <- the head's last layer (as mvn_deconv4s2) and process_features,
  *                           mvn/models/triangulation.py:238-240, :345, in one launch
+ *   mvn_conv1x1, mvn_conv3x3 <- mvn/models/pose_resnet.py:57-95 (the Bottleneck of the ResNet trunk's
+ *                           layer1 .. layer4: its three convolutions with their BatchNorms, the
+ *                           residual with its downsample, and the ReLUs; eval mode)
  *
  * Conventions
  *   - Every buffer is caller-owned device memory (hipMalloc / torch), contiguous,
@@ -626,6 +629,82 @@ size_t mvn_deconv4s2_project_weight_bytes(void);
 int mvn_deconv4s2_project(const void* x, const void* weight_packed, const float* scale, const float* shift,
                           const void* proj_packed, const float* bias, void* out, int out_dtype, int64_t n_images,
                           int cin, int H, int W, void* stream);
+
+/*
+ * The 1x1 convolutions of the backbone's ResNet trunk (mvn/models/pose_resnet.py:57-95, Bottleneck:
+ * conv1 + bn1 + relu, and conv3 + bn3 + the residual + relu), eval mode, on v_mfma_f32_16x16x32_bf16
+ * (DESIGN.md §4.18).  Per image n, pixel (oy, ox) of the H x W map and output channel co:
+ *   acc = sum over ci of x[n, oy, ox, ci] * w[co][ci]
+ *         (products of bf16 operands, accumulated in f32 on the MFMA, summation order free)
+ *   pre = fmaf(acc, scale[co], shift[co])
+ *   r   = pre                                                    skip_mode MVN_SKIP_NONE
+ *       = pre + float(skip[n, oy, ox, co])                       MVN_SKIP_IDENTITY
+ *       = pre + fmaf(acc_s, skip_scale[co], skip_shift[co])      MVN_SKIP_POINTWISE, with
+ *         acc_s = sum over cs of skip[n, s oy, s ox, cs] * w_s[co][cs], s = skip_stride: the block's
+ *         downsample (Conv2d 1x1 with stride s + BatchNorm2d), fused
+ *   y   = r <= 0 ? +0 : r                                        (a NaN stays NaN)
+ *   out = y rounded once to bf16 (nearest-even)
+ *   x              (n_images, H, W, cin) bf16, channels-last
+ *   cin, cout, skip_cin   multiples of 64 in [64, 2048]
+ *   weight_packed  mvn_conv1x1_packed_weight_bytes(cin, cout) = (cin / 32) * (cout / 16) * 64 * 8 * 2 bytes:
+ *                  bf16 as [kp 0..cin/32-1][m 0..cout/16-1][lane 0..63][j 0..7]
+ *                    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j]
+ *                  (w the Conv2d weight (cout, cin, 1, 1), rounded to bf16)
+ *   scale, shift   (cout) f32: the BatchNorm folded
+ *   skip           NULL (NONE); (n_images, H, W, cout) bf16 (IDENTITY); (n_images, skip_H, skip_W,
+ *                  skip_cin) bf16 (POINTWISE), where H = (skip_H - 1) / skip_stride + 1 in integer
+ *                  division and the same for W, skip_stride 1 or 2
+ *   skip_weight_packed, skip_scale, skip_shift   POINTWISE only (NULL otherwise): w_s packed as
+ *                  weight_packed with skip_cin for cin, and the downsample's folded BatchNorm (cout)
+ *   skip_cin, skip_H, skip_W, skip_stride   read with POINTWISE only
+ *   out            (n_images, H, W, cout) bf16, channels-last
+ * Every tensor stays below 2^31 bytes (one buffer resource each) and every pointer is 16-byte
+ * aligned.  The order of the sums is the same for the same launch: deterministic, no atomics.  A
+ * NaN or infinite x[n, oy, ox, .] reaches out[n, oy, ox, .] only, a non-finite skip pixel the one
+ * output pixel that reads it.  No load touches a byte outside an operand (range-checked buffer
+ * resources for x and the pointwise skip) and no store a byte outside out.
+ * Checked before any HIP call, all MVN_ERR_ARG: a null required pointer, an unknown skip_mode, skip
+ * arguments that contradict the mode, a channel count outside the set, n_images < 0, H < 1 or W < 1,
+ * a tensor of 2^31 bytes or more, with POINTWISE a stride other than 1 or 2 or a skip extent that
+ * does not give H x W, a pointer off its alignment.  n_images == 0 returns MVN_OK without a launch.
+ * The size function returns 0 for a channel count outside the set.  Stream-ordered, allocates
+ * nothing, reentrant.
+ */
+size_t mvn_conv1x1_packed_weight_bytes(int cin, int cout);
+int mvn_conv1x1(const void* x, const void* weight_packed, const float* scale, const float* shift, int skip_mode,
+                const void* skip, const void* skip_weight_packed, const float* skip_scale, const float* skip_shift,
+                int skip_cin, int skip_H, int skip_W, int skip_stride, void* out, int64_t n_images, int H, int W,
+                int cin, int cout, void* stream);
+
+/*
+ * The 3x3 convolution of the trunk's Bottleneck (conv2 + bn2 + relu; padding 1, stride 1 or 2, as
+ * many outputs as inputs), eval mode, on v_mfma_f32_16x16x32_bf16.  The output is
+ * (n_images, Ho, Wo, channels) with Ho = (H - 1) / stride + 1 and Wo = (W - 1) / stride + 1 in integer
+ * division.  Per image n, output pixel (oy, ox) and output channel co:
+ *   acc = sum over ci and the taps (ky, kx) in 0..2 with iy = stride oy - 1 + ky in [0, H) and
+ *         ix = stride ox - 1 + kx in [0, W) of x[n, iy, ix, ci] * w[co][ci][ky][kx]
+ *         (a tap outside the image contributes zero and never reads the neighbouring image;
+ *         products of bf16 operands, accumulated in f32 on the MFMA, summation order free)
+ *   y   = relu_keep_nan(fmaf(acc, scale[co], shift[co])), rounded once to bf16
+ *   x              (n_images, H, W, channels) bf16, channels-last
+ *   channels       a multiple of 64 in [64, 512]
+ *   weight_packed  mvn_conv3x3_packed_weight_bytes(channels) = 9 * (channels / 32) * (channels / 16) * 64 * 8 * 2
+ *                  bytes: bf16 as [tap = ky*3 + kx][kp 0..channels/32-1][m 0..channels/16-1][lane 0..63][j 0..7]
+ *                    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][ky][kx]
+ *                  (w the Conv2d weight (channels, channels, 3, 3), rounded to bf16)
+ *   scale, shift   (channels) f32: the BatchNorm folded
+ * x and out stay below 2^31 bytes and every pointer is 16-byte aligned.  Deterministic.  A NaN or
+ * infinite input pixel (iy, ix) reaches exactly the output pixels (oy, ox) with |stride oy - iy| <= 1
+ * and |stride ox - ix| <= 1 of its own image, in all channels.  No load touches a byte outside x and
+ * no store a byte outside out.
+ * Checked before any HIP call, all MVN_ERR_ARG: a null pointer, channels outside the set, a stride
+ * other than 1 or 2, n_images < 0, H < 1 or W < 1, a tensor of 2^31 bytes or more, a pointer off its
+ * alignment.  n_images == 0 returns MVN_OK without a launch.  The size function returns 0 for
+ * channels outside the set.  Stream-ordered, allocates nothing, reentrant.
+ */
+size_t mvn_conv3x3_packed_weight_bytes(int channels);
+int mvn_conv3x3(const void* x, const void* weight_packed, const float* scale, const float* shift, void* out,
+                int64_t n_images, int H, int W, int channels, int stride, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

@@ -483,6 +483,59 @@ def _(x, packed, scale, shift, proj, bias, out_dtype):
     return x.new_empty((M, FEATURE_COUT, 2 * H, 2 * W), dtype=_CODE_DTYPE[out_dtype])
 
 
+# --------------------------------------------------------------------------- ResNet trunk (Bottleneck convolutions)
+@_op("conv1x1")
+def conv1x1(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, skip_mode: int, skip: Optional[Tensor],
+            skip_packed: Optional[Tensor], skip_scale: Optional[Tensor], skip_shift: Optional[Tensor],
+            skip_stride: int) -> Tensor:
+    """x (M,H,W,Cin) bf16 channels-last -> relu(bn(conv1x1(x)) + skip term) as (M,H,W,Cout) bf16, Cout =
+    len(scale); skip (M,H,W,Cout) with MVN_SKIP_IDENTITY, (M,Hs,Ws,Cs) with its packed 1x1 weights, scale,
+    shift and stride with MVN_SKIP_POINTWISE (csrc/bottleneck.hip)."""
+    _require_gpu(x, packed, scale, shift, skip, skip_packed, skip_scale, skip_shift)
+    M, H, W, cin = x.shape
+    cout = scale.shape[0]
+    out = torch.empty((M, H, W, cout), dtype=torch.bfloat16, device=x.device)
+    if M == 0:                            # empty batch: nothing to launch
+        return out
+    pw = int(skip_mode) == _lib.MVN_SKIP_POINTWISE
+    code = _lib.load().mvn_conv1x1(x.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(skip_mode),
+                                   _ptr(skip), _ptr(skip_packed), _ptr(skip_scale), _ptr(skip_shift),
+                                   skip.shape[3] if pw else 0, skip.shape[1] if pw else 0, skip.shape[2] if pw else 0,
+                                   int(skip_stride), out.data_ptr(), M, H, W, cin, cout, _stream(x))
+    _lib.check(code, "mvn_conv1x1")
+    return out
+
+
+@conv1x1.register_fake
+def _(x, packed, scale, shift, skip_mode, skip, skip_packed, skip_scale, skip_shift, skip_stride):
+    return x.new_empty((*x.shape[:3], scale.shape[0]), dtype=torch.bfloat16)
+
+
+def _conv3x3_out_shape(x: Tensor, stride: int):
+    M, H, W, C = x.shape
+    return (M, (H - 1) // stride + 1, (W - 1) // stride + 1, C)
+
+
+@_op("conv3x3")
+def conv3x3(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, stride: int) -> Tensor:
+    """x (M,H,W,C) bf16 channels-last -> relu(bn(conv3x3(x, padding 1, stride))) as (M,Ho,Wo,C) bf16
+    (csrc/bottleneck.hip)."""
+    _require_gpu(x, packed, scale, shift)
+    M, H, W, C = x.shape
+    out = torch.empty(_conv3x3_out_shape(x, int(stride)), dtype=torch.bfloat16, device=x.device)
+    if M == 0:                            # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_conv3x3(x.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr(),
+                                   M, H, W, C, int(stride), _stream(x))
+    _lib.check(code, "mvn_conv3x3")
+    return out
+
+
+@conv3x3.register_fake
+def _(x, packed, scale, shift, stride):
+    return x.new_empty(_conv3x3_out_shape(x, stride), dtype=torch.bfloat16)
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,

@@ -7,7 +7,9 @@ in the same launch: the 256-channel maps are not written.
 
 ``DeconvHeadEval`` is the head alone, from ``layer4``'s output to ``(heatmaps, features)``;
 ``BackboneEval`` is the reference's ``PoseResNet.forward`` with its own trunk modules in front of
-it.  The ResNet trunk and the confidence heads stay with torch.  Eval mode, inference-only.
+it.  The confidence heads stay with torch, and by default so does the ResNet trunk;
+``BackboneEval.from_reference(..., trunk="kernels")`` runs ``layer1`` .. ``layer4`` on ``resnet.TrunkEval``
+(DESIGN.md §4.18).  Eval mode, inference-only.
 """
 from __future__ import annotations
 
@@ -335,28 +337,46 @@ class BackboneEval(nn.Module):
     the backbone's own objects (not copies) and must live on the device of the input; call under
     ``torch.no_grad()``."""
 
-    def __init__(self, trunk, head, alg_confidences=None, vol_confidences=None):
+    def __init__(self, trunk, head, alg_confidences=None, vol_confidences=None, cast_for_confidences=False):
         super().__init__()
         self.trunk = trunk
         self.head = head
         self.alg_confidences = alg_confidences
         self.vol_confidences = vol_confidences
+        self.cast_for_confidences = bool(cast_for_confidences)
 
     @classmethod
     def from_reference(cls, backbone, device="cuda", feature_dtype=torch.bfloat16, heatmaps=True,
-                       process_features=None):
+                       process_features=None, trunk="torch"):
+        """``trunk="torch"`` (the default) keeps the backbone's own ``conv1`` ... ``layer4``; ``trunk="kernels"``
+        runs ``layer1`` .. ``layer4`` through ``resnet.TrunkEval``, whose bfloat16
+        channels-last output the head reads without a copy and the confidence heads, which stay torch
+        modules, get cast to their parameters' dtype."""
+        if trunk not in ("torch", "kernels"):
+            raise ValueError(f"BackboneEval: trunk must be 'torch' or 'kernels', got {trunk!r}")
         missing = [n for n in _TRUNK if not isinstance(getattr(backbone, n, None), nn.Module)]
         if missing:
             raise RuntimeError(f"BackboneEval: expected the trunk modules {', '.join(_TRUNK)}; {type(backbone).__name__} "
                                f"has no {', '.join(missing)}")
-        trunk = nn.Sequential(*(getattr(backbone, n) for n in _TRUNK))
+        if trunk == "kernels":
+            from .resnet import TrunkEval
+            trunk_module = TrunkEval.from_reference(backbone, device=device)
+        else:
+            trunk_module = nn.Sequential(*(getattr(backbone, n) for n in _TRUNK))
         head = DeconvHeadEval.from_reference(backbone, device, feature_dtype, heatmaps, process_features)
-        return cls(trunk, head, getattr(backbone, "alg_confidences", None), getattr(backbone, "vol_confidences", None))
+        return cls(trunk_module, head, getattr(backbone, "alg_confidences", None),
+                   getattr(backbone, "vol_confidences", None), cast_for_confidences=trunk == "kernels")
 
     def forward(self, x):
         _inference_only("BackboneEval", x, instead="the backbone itself, which autograd records")
         x = self.trunk(x)
-        alg = self.alg_confidences(x) if self.alg_confidences is not None else None
-        vol = self.vol_confidences(x) if self.vol_confidences is not None else None
+        xc = x
+        if self.cast_for_confidences:     # one cast of the kernels' bfloat16 output for both heads
+            heads = [h for h in (self.alg_confidences, self.vol_confidences) if h is not None]
+            p = next((p for h in heads for p in h.parameters()), None)
+            if p is not None and p.dtype != x.dtype:
+                xc = x.to(p.dtype)
+        alg = self.alg_confidences(xc) if self.alg_confidences is not None else None
+        vol = self.vol_confidences(xc) if self.vol_confidences is not None else None
         heatmaps, features = self.head(x)
         return heatmaps, features, alg, vol
