@@ -50,6 +50,8 @@
  *   mvn_conv1x1, mvn_conv3x3 <- mvn/models/pose_resnet.py:57-95 (the Bottleneck of the ResNet trunk's
  *                           layer1 .. layer4: its three convolutions with their BatchNorms, the
  *                           residual with its downsample, and the ReLUs; eval mode)
+ *   mvn_stem               <- mvn/models/pose_resnet.py:205-209, 294-297 (conv1 + bn1 + relu + maxpool
+ *                           of the ResNet; eval mode)
  *
  * Conventions
  *   - Every buffer is caller-owned device memory (hipMalloc / torch), contiguous,
@@ -705,6 +707,46 @@ int mvn_conv1x1(const void* x, const void* weight_packed, const float* scale, co
 size_t mvn_conv3x3_packed_weight_bytes(int channels);
 int mvn_conv3x3(const void* x, const void* weight_packed, const float* scale, const float* shift, void* out,
                 int64_t n_images, int H, int W, int channels, int stride, void* stream);
+
+/*
+ * The stem of the backbone's ResNet (mvn/models/pose_resnet.py:205-209, 294-297): Conv2d(3, 64, 7,
+ * stride 2, padding 3) + BatchNorm2d + ReLU + MaxPool2d(3, stride 2, padding 1), eval mode, in one
+ * launch on v_mfma_f32_16x16x32_bf16.  With Hc = (H - 1) / 2 + 1, Hp = (Hc - 1) / 2 + 1
+ * in integer division and the same for W, per image n and channel co:
+ *   c[n, co, cy, cx] = sum over ci in 0..2 and the taps (ky, kx) in 0..6 with iy = 2 cy - 3 + ky in [0, H)
+ *         and ix = 2 cx - 3 + kx in [0, W) of bf16(images[n, ci, iy, ix]) * w[co][ci][ky][kx]
+ *         (a tap outside the image contributes zero and never reads the neighbouring plane or image;
+ *         products of bf16 operands, accumulated in f32 on the MFMA, summation order free)
+ *   a   = relu_keep_nan(fmaf(c, scale[co], shift[co]))           f32; r <= 0 ? +0 : r, a NaN stays NaN
+ *   p[n, py, px, co] = the maximum of a over cy in {2 py - 1, 2 py, 2 py + 1} within [0, Hc) and cx likewise
+ *         within [0, Wc), with torch's update `v > m || isnan(v)`: a NaN in the window gives a NaN
+ *   out = p rounded once to bf16 (nearest-even).  The kernel rounds a BEFORE the maximum (its map of a
+ *         is held as bf16); rounding is monotone, so these are the bits of rounding behind the maximum.
+ *   images         (n_images, 3, H, W) in_dtype (MVN_DTYPE_F32 | MVN_DTYPE_BF16), contiguous NCHW; an
+ *                  f32 image is rounded once to bf16 in the kernel (nearest-even, NaN and +-inf kept)
+ *   weight_packed  mvn_stem_packed_weight_bytes() = 6 * 4 * 64 * 8 * 2 = 24576 bytes: bf16 as
+ *                  [kp 0..5][m 0..3][lane 0..63][j 0..7] = A[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j]
+ *                  with A (64, 192): A[co][24 ky + 3 kx + ci] = w[co][ci][ky][kx] for ky, kx in 0..6 and
+ *                  ci in 0..2 (w the Conv2d weight (64, 3, 7, 7), rounded to bf16), and zero in every
+ *                  other slot: 24 ky + 21 .. 24 ky + 23 of each tap row and 168 .. 191.  The kernel
+ *                  clears the pixel operand of those slots as well: they carry nothing, whatever the
+ *                  weights there and the pixels beside the footprint hold.
+ *   scale, shift   (64) f32: the BatchNorm (and a convolution bias) folded
+ *   out            (n_images, Hp, Wp, 64) bf16, channels-last
+ * images and out stay below 2^31 bytes.  weight_packed, scale, shift and out are 16-byte aligned; images
+ * needs the alignment of its element only.  Deterministic: the order of the sums is fixed, no atomics.
+ * A NaN or infinite input pixel (iy, ix) reaches exactly the outputs (py, px) with a cy in {2 py - 1 ..
+ * 2 py + 1} within [0, Hc) with |2 cy - iy| <= 3, and likewise in x, of its own image, in all channels
+ * (an infinity against a zero weight is a NaN, as in torch); a -inf or any value the ReLU removes does
+ * not survive the pool.  No load touches a byte outside an operand (one range-checked buffer
+ * resource over images) and no store a byte outside out.
+ * Checked before any HIP call, all MVN_ERR_ARG: a null pointer, an unknown in_dtype, n_images < 0, H < 1
+ * or W < 1, a tensor of 2^31 bytes or more, a pointer off its alignment.  n_images == 0 returns MVN_OK
+ * without a launch.  Stream-ordered, allocates nothing, reentrant.
+ */
+size_t mvn_stem_packed_weight_bytes(void);
+int mvn_stem(const void* images, int in_dtype, const void* weight_packed, const float* scale, const float* shift,
+             void* out, int64_t n_images, int H, int W, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

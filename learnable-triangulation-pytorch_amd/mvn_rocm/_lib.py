@@ -98,6 +98,8 @@ SIGNATURES = {
                     + [_c_int] * 4 + [_c_void_p]),
     "mvn_conv3x3_packed_weight_bytes": (_c_size_t, [_c_int]),
     "mvn_conv3x3": (_c_int, [_c_void_p] * 5 + [_c_i64] + [_c_int] * 4 + [_c_void_p]),
+    "mvn_stem_packed_weight_bytes": (_c_size_t, []),
+    "mvn_stem": (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 4 + [_c_i64, _c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
                                         _c_void_p, _c_void_p] + [_c_int] * 8 + [_c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward_workspace_bytes": (_c_size_t, [_c_int] * 5),

@@ -536,6 +536,35 @@ def _(x, packed, scale, shift, stride):
     return x.new_empty(_conv3x3_out_shape(x, stride), dtype=torch.bfloat16)
 
 
+# --------------------------------------------------------------------------- ResNet stem
+STEM_COUT = 64
+
+
+def _stem_out_shape(images: Tensor):
+    M, _, H, W = images.shape
+    return (M, ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1, STEM_COUT)
+
+
+@_op("stem")
+def stem(images: Tensor, packed: Tensor, scale: Tensor, shift: Tensor) -> Tensor:
+    """images (M,3,H,W) f32|bf16 contiguous NCHW -> maxpool(relu(bn(conv7x7(images, stride 2, padding 3))), 3, 2, 1)
+    as (M,Hp,Wp,64) bf16 channels-last (csrc/stem.hip)."""
+    _require_gpu(images, packed, scale, shift)
+    M, _, H, W = images.shape
+    out = torch.empty(_stem_out_shape(images), dtype=torch.bfloat16, device=images.device)
+    if M == 0:                            # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_stem(images.data_ptr(), _DTYPE_CODE[images.dtype], packed.data_ptr(), scale.data_ptr(),
+                                shift.data_ptr(), out.data_ptr(), M, H, W, _stream(images))
+    _lib.check(code, "mvn_stem")
+    return out
+
+
+@stem.register_fake
+def _(images, packed, scale, shift):
+    return images.new_empty(_stem_out_shape(images), dtype=torch.bfloat16)
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,

@@ -347,20 +347,26 @@ class BackboneEval(nn.Module):
 
     @classmethod
     def from_reference(cls, backbone, device="cuda", feature_dtype=torch.bfloat16, heatmaps=True,
-                       process_features=None, trunk="torch"):
+                       process_features=None, trunk="torch", stem="torch"):
         """``trunk="torch"`` (the default) keeps the backbone's own ``conv1`` ... ``layer4``; ``trunk="kernels"``
         runs ``layer1`` .. ``layer4`` through ``resnet.TrunkEval``, whose bfloat16
         channels-last output the head reads without a copy and the confidence heads, which stay torch
-        modules, get cast to their parameters' dtype."""
+        modules, get cast to their parameters' dtype.  ``stem`` is passed on to ``TrunkEval``: ``"kernels"``
+        runs ``conv1, bn1, relu, maxpool`` as one launch too and needs ``trunk="kernels"``."""
         if trunk not in ("torch", "kernels"):
             raise ValueError(f"BackboneEval: trunk must be 'torch' or 'kernels', got {trunk!r}")
+        if stem not in ("torch", "kernels"):
+            raise ValueError(f"BackboneEval: stem must be 'torch' or 'kernels', got {stem!r}")
+        if stem == "kernels" and trunk != "kernels":
+            raise ValueError("BackboneEval: stem='kernels' needs trunk='kernels': the kernel stem writes channels-last "
+                             f"bfloat16 for TrunkEval, got trunk={trunk!r}")
         missing = [n for n in _TRUNK if not isinstance(getattr(backbone, n, None), nn.Module)]
         if missing:
             raise RuntimeError(f"BackboneEval: expected the trunk modules {', '.join(_TRUNK)}; {type(backbone).__name__} "
                                f"has no {', '.join(missing)}")
         if trunk == "kernels":
             from .resnet import TrunkEval
-            trunk_module = TrunkEval.from_reference(backbone, device=device)
+            trunk_module = TrunkEval.from_reference(backbone, device=device, stem=stem)
         else:
             trunk_module = nn.Sequential(*(getattr(backbone, n) for n in _TRUNK))
         head = DeconvHeadEval.from_reference(backbone, device, feature_dtype, heatmaps, process_features)

@@ -175,16 +175,17 @@ class VolumetricModelEval(nn.Module):
 
     @classmethod
     def from_reference(cls, model, device="cuda", feature_dtype=torch.bfloat16, half_res="kernels", deep="kernels",
-                       precision=None, fused=FUSED_DEFAULT, trunk="torch"):
+                       precision=None, fused=FUSED_DEFAULT, trunk="torch", stem="torch"):
         """``model.backbone`` through ``BackboneEval.from_reference`` (``heatmaps=False``; with ``fused`` it
         is given ``model.process_features``; ``trunk`` is passed on: ``"kernels"`` runs the ResNet stages on
-        ``resnet.TrunkEval``) and the rest of ``model`` through
-        ``VolumetricEval.from_reference``.  ``fused`` defaults to what was measured faster (DESIGN.md
+        ``resnet.TrunkEval``, DESIGN.md §4.18, and with it ``stem="kernels"`` the stem in one launch, §4.19)
+        and the rest of ``model`` through ``VolumetricEval.from_reference``.  ``fused`` defaults to what was measured faster (DESIGN.md
         §4.17)."""
         from .backbone import BackboneEval
         vol = VolumetricEval.from_reference(model, device, feature_dtype, half_res, deep, precision)
         bb = BackboneEval.from_reference(model.backbone, device, feature_dtype, heatmaps=False,
-                                         process_features=model.process_features if fused else None, trunk=trunk)
+                                         process_features=model.process_features if fused else None, trunk=trunk,
+                                         stem=stem)
         return cls(bb, vol, fused)
 
     def forward(self, images, proj_matricies, coord_volumes):

@@ -7,9 +7,10 @@ blocks, each three convolutions with a BatchNorm behind them, a residual (the in
     conv1x1 (conv1 + bn1 + relu) -> conv3x3 (conv2 + bn2 + relu, the block's stride)
     -> conv1x1 (conv3 + bn3 + the residual + relu; the downsample runs inside this launch)
 
-``TrunkEval`` is the whole trunk: the stem (``conv1, bn1, relu, maxpool``) stays the backbone's own
-torch modules, one cast-and-permute pass makes its output channels-last bfloat16, and the four stages
-run on the kernels.  Eval mode, inference-only.
+``TrunkEval`` is the whole trunk: by default the stem (``conv1, bn1, relu, maxpool``) stays the backbone's
+own torch modules, one cast-and-permute pass makes its output channels-last bfloat16, and the four stages
+run on the kernels.  With ``stem="kernels"`` the stem and that pass are one launch as well (csrc/stem.hip,
+``StemEval``).  Eval mode, inference-only.
 """
 from __future__ import annotations
 
@@ -66,6 +67,22 @@ def pack_conv3x3_weight(w):
     C = w.shape[0]
     _check_c("pack_conv3x3_weight", "C", C, MAX_C3)
     return _pack_mfma_a(w.permute(2, 3, 0, 1).reshape(9, C, C))
+
+
+STEM_CIN, STEM_COUT, STEM_K = 3, 64, 7
+STEM_ROW_SLOTS, STEM_K_SLOTS = 24, 192    # K-slots of a tap row (21 real) and of the whole packed K axis (168 real)
+
+
+def pack_stem_weight(w):
+    """(64, 3, 7, 7) float64 Conv2d weight -> (6, 4, 64, 8) bf16 as mvn_stem reads it:
+    [kp][m][lane][j] = A[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j] with A (64, 192),
+    A[co][24 ky + 3 kx + ci] = w[co][ci][ky][kx] and zero in every other slot (24 ky + 21 .. 24 ky + 23 and
+    168 .. 191)."""
+    if w.dim() != 4 or tuple(w.shape) != (STEM_COUT, STEM_CIN, STEM_K, STEM_K):
+        raise RuntimeError(f"expected a ({STEM_COUT}, {STEM_CIN}, {STEM_K}, {STEM_K}) Conv2d weight, got {tuple(w.shape)}")
+    rows = w.permute(0, 2, 3, 1).reshape(STEM_COUT, STEM_K, STEM_K * STEM_CIN)           # [co][ky][3 kx + ci]
+    rows = nn.functional.pad(rows, (0, STEM_ROW_SLOTS - STEM_K * STEM_CIN)).reshape(STEM_COUT, STEM_K * STEM_ROW_SLOTS)
+    return _pack_mfma_a(nn.functional.pad(rows, (0, STEM_K_SLOTS - STEM_K * STEM_ROW_SLOTS)))
 
 
 # ----------------------------------------------------------------------------- the fold
@@ -149,6 +166,33 @@ def fold_bottleneck(block, device="cuda"):
     return BottleneckParams(_fold_conv(block.conv1, block.bn1, pack_conv1x1_weight, dev),
                             _fold_conv(block.conv2, block.bn2, pack_conv3x3_weight, dev),
                             _fold_conv(block.conv3, block.bn3, pack_conv1x1_weight, dev), down, stride)
+
+
+def fold_stem(conv1, bn1, relu, maxpool, device="cuda"):
+    """The reference's eval-mode stem (pose_resnet.py:205-209): ``Conv2d(3, 64, 7, stride=2, padding=3)`` with no
+    dilation and one group, ``BatchNorm2d(64)`` with running statistics, ``nn.ReLU`` and
+    ``MaxPool2d(kernel_size=3, stride=2, padding=1)`` with dilation 1, ``ceil_mode=False``,
+    ``return_indices=False`` -> ``ConvParams`` on ``device``: the weight rounded once to bf16 and packed
+    (``pack_stem_weight``), the BatchNorm (and a conv bias, if any) folded in float64 and rounded once to f32.
+    Anything else raises a RuntimeError naming what was found."""
+    what = "fold_stem"
+    _check_conv_bn(f"{what}: conv1", conv1, bn1, STEM_K, 3, (2,))
+    if (conv1.in_channels, conv1.out_channels) != (STEM_CIN, STEM_COUT):
+        raise RuntimeError(f"{what}: expected conv1 to be Conv2d({STEM_CIN}, {STEM_COUT}, {STEM_K}), got "
+                           f"Conv2d({conv1.in_channels}, {conv1.out_channels}, {STEM_K})")
+    if not isinstance(relu, nn.ReLU):
+        raise RuntimeError(f"{what}: expected an nn.ReLU behind bn1, got {type(relu).__name__}")
+    if not isinstance(maxpool, nn.MaxPool2d):
+        raise RuntimeError(f"{what}: expected a MaxPool2d behind the ReLU, got {type(maxpool).__name__}")
+    found = dict(kernel_size=_pair(maxpool.kernel_size), stride=_pair(maxpool.stride), padding=_pair(maxpool.padding),
+                 dilation=_pair(maxpool.dilation), ceil_mode=bool(maxpool.ceil_mode),
+                 return_indices=bool(maxpool.return_indices))
+    want = dict(kernel_size=(3, 3), stride=(2, 2), padding=(1, 1), dilation=(1, 1), ceil_mode=False, return_indices=False)
+    bad = {n: v for n, v in found.items() if v != want[n]}
+    if bad:
+        raise RuntimeError(f"{what}: expected MaxPool2d(kernel_size=3, stride=2, padding=1) with dilation 1, ceil_mode=False "
+                           "and return_indices=False, got " + ", ".join(f"{n}={v}" for n, v in bad.items()))
+    return _fold_conv(conv1, bn1, pack_stem_weight, torch.device(device))
 
 
 # ----------------------------------------------------------------------------- launches
@@ -235,6 +279,30 @@ def conv3x3(x_cl, packed, scale, shift, stride=1):
     return _ops.call(_ops.conv3x3, _aligned(x_cl), _aligned(packed), _aligned(scale), _aligned(shift), int(stride))
 
 
+def stem(images, packed, scale, shift):
+    """One launch of mvn_stem: images (M, 3, H, W) float32 or bfloat16 ->
+    ``max_pool2d(relu(conv7x7(bf16(images), stride 2, padding 3) * scale + shift), 3, 2, 1)`` as
+    (M, Hp, Wp, 64) bfloat16 channels-last, Hp = ((H - 1) // 2) // 2 + 1 and the same for W; ``packed`` from
+    ``pack_stem_weight``.  A non-contiguous tensor (channels_last included) is made contiguous and a
+    misaligned view of the weights is copied.  GPU only; inference-only."""
+    what = "stem"
+    _inference_only(what, images, packed, scale, shift, instead="the backbone's own conv1, bn1, relu and maxpool, "
+                    "which autograd records")
+    if images.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{what}: images must be float32 or bfloat16, got {images.dtype}")
+    if images.dim() != 4 or images.shape[1] != STEM_CIN:
+        raise RuntimeError(f"{what}: images must be (M, {STEM_CIN}, H, W), got {tuple(images.shape)}")
+    M, _, H, W = images.shape
+    if H < 1 or W < 1 or M * STEM_CIN * H * W * images.element_size() > MAX_BYTES:
+        raise RuntimeError(f"{what}: images must have H, W >= 1 and stay below 2^31 bytes, got {tuple(images.shape)}")
+    _check_folded(what, "the weights", ConvParams(packed, scale, shift), (STEM_K_SLOTS // 32, STEM_COUT // 16, 64, 8),
+                  STEM_COUT)
+    out_shape = (M, ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1, STEM_COUT)
+    if out_shape[0] * out_shape[1] * out_shape[2] * STEM_COUT * 2 > MAX_BYTES:
+        raise RuntimeError(f"{what}: the output must stay below 2^31 bytes, got {out_shape}")
+    return _ops.call(_ops.stem, images.contiguous(), _aligned(packed), _aligned(scale), _aligned(shift))
+
+
 def bottleneck(x_cl, params):
     """An eval-mode Bottleneck in three launches: x_cl (M, H, W, Cin) bfloat16 channels-last -> (M, Ho, Wo, Cout)
     bfloat16 with ``params`` from ``fold_bottleneck``; the residual is x_cl itself, or x_cl through the
@@ -289,6 +357,34 @@ _STEM = ("conv1", "bn1", "relu", "maxpool")
 _LAYERS = ("layer1", "layer2", "layer3", "layer4")
 
 
+class StemEval(nn.Module):
+    """Eval-mode replacement of the reference's ``conv1, bn1, relu, maxpool`` in one launch (``stem``):
+    ``StemEval.from_reference(backbone)(images (M, 3, H, W) float32 or bfloat16)`` returns the pooled map as
+    (M, Hp, Wp, 64) bfloat16 channels-last, what the first ``BottleneckCL`` reads.  The parameters are copied."""
+
+    def __init__(self, params):
+        super().__init__()
+        p = ConvParams(*params)
+        self.register_buffer("packed", p.packed)
+        self.register_buffer("scale", p.scale)
+        self.register_buffer("shift", p.shift)
+
+    @classmethod
+    def from_reference(cls, backbone, device="cuda"):
+        missing = [n for n in _STEM if not isinstance(getattr(backbone, n, None), nn.Module)]
+        if missing:
+            raise RuntimeError(f"StemEval: expected the stem modules {', '.join(_STEM)}; {type(backbone).__name__} has no "
+                               f"{', '.join(missing)}")
+        return cls(fold_stem(*(getattr(backbone, n) for n in _STEM), device=device))
+
+    @property
+    def params(self):
+        return ConvParams(self.packed, self.scale, self.shift)
+
+    def forward(self, images):
+        return stem(images, *self.params)
+
+
 class TrunkEval(nn.Module):
     """``conv1`` .. ``layer4`` of the reference's ``PoseResNet.forward`` (pose_resnet.py:293-310), eval mode:
     ``module(images (M, 3, H, W))`` returns ``layer4``'s output as an (M, C, h, w) bfloat16 tensor in
@@ -300,7 +396,9 @@ class TrunkEval(nn.Module):
     2. one cast-and-permute pass: channels-last bfloat16;
     3. every ``Bottleneck`` of ``layer1`` .. ``layer4``: three launches (``bottleneck``).
 
-    The blocks' parameters are copied: later changes to the backbone do not reach them."""
+    With ``stem="kernels"`` steps 1 and 2 are one launch of ``StemEval``, whose output the
+    first block reads as it is.  The blocks' parameters are copied: later changes to the backbone do not reach
+    them."""
 
     def __init__(self, stem, blocks):
         super().__init__()
@@ -308,11 +406,13 @@ class TrunkEval(nn.Module):
         self.blocks = nn.ModuleList(blocks)
 
     @classmethod
-    def from_reference(cls, backbone, device="cuda"):
-        """``backbone.conv1, bn1, relu, maxpool`` as they are and ``backbone.layer1`` .. ``layer4``, each a
-        Sequential of ``Bottleneck`` blocks whose channels chain; anything else raises and names what it
-        found."""
+    def from_reference(cls, backbone, device="cuda", stem="torch"):
+        """``backbone.conv1, bn1, relu, maxpool`` as they are (``stem="torch"``, the default) or folded into a
+        ``StemEval`` (``stem="kernels"``), and ``backbone.layer1`` .. ``layer4``, each a Sequential of
+        ``Bottleneck`` blocks whose channels chain; anything else raises and names what it found."""
         what = "TrunkEval"
+        if stem not in ("torch", "kernels"):
+            raise ValueError(f"{what}: stem must be 'torch' or 'kernels', got {stem!r}")
         missing = [n for n in _STEM + _LAYERS if not isinstance(getattr(backbone, n, None), nn.Module)]
         if missing:
             raise RuntimeError(f"{what}: expected the trunk modules {', '.join(_STEM + _LAYERS)}; {type(backbone).__name__} "
@@ -333,10 +433,18 @@ class TrunkEval(nn.Module):
                                        f"conv1.in_channels={b.cin}")
                 c = b.cout
                 blocks.append(b)
+        if stem == "kernels":
+            try:
+                return cls(StemEval.from_reference(backbone, device=device), blocks)
+            except RuntimeError as e:
+                raise RuntimeError(f"{what}: {e}") from None
         return cls(nn.Sequential(*(getattr(backbone, n) for n in _STEM)), blocks)
 
     def channels_last(self, x):
-        """The stem and the one cast-and-permute pass: images -> (M, h, w, C) bfloat16."""
+        """The stem and the one cast-and-permute pass, or the one launch of a ``StemEval``: images ->
+        (M, h, w, C) bfloat16."""
+        if isinstance(self.stem, StemEval):
+            return self.stem(x)
         h = self.stem(x).permute(0, 2, 3, 1)
         return torch.empty(h.shape, dtype=torch.bfloat16, device=h.device).copy_(h)
 
