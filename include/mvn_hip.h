@@ -52,6 +52,9 @@
  *                           residual with its downsample, and the ReLUs; eval mode)
  *   mvn_stem               <- mvn/models/pose_resnet.py:205-209, 294-297 (conv1 + bn1 + relu + maxpool
  *                           of the ResNet; eval mode)
+ *   mvn_conv3x3_pool, mvn_confidence_tail <- mvn/models/pose_resnet.py:140-174 (GlobalAveragePoolingHead:
+ *                           a 3x3 convolution + BatchNorm2d + MaxPool2d(2) + ReLU stage, and the mean
+ *                           with the three Linear layers and the Sigmoid; eval mode)
  *
  * Conventions
  *   - Every buffer is caller-owned device memory (hipMalloc / torch), contiguous,
@@ -747,6 +750,85 @@ int mvn_conv3x3(const void* x, const void* weight_packed, const float* scale, co
 size_t mvn_stem_packed_weight_bytes(void);
 int mvn_stem(const void* images, int in_dtype, const void* weight_packed, const float* scale, const float* shift,
              void* out, int64_t n_images, int H, int W, void* stream);
+
+/*
+ * One convolution stage of the backbone's confidence heads (mvn/models/pose_resnet.py:144-153,
+ * GlobalAveragePoolingHead.features): Conv2d(cin, cout, 3, padding 1) with bias + BatchNorm2d +
+ * MaxPool2d(2) + ReLU, eval mode, in one launch on v_mfma_f32_16x16x32_bf16.  With
+ * Hp = H / 2 and Wp = W / 2 in integer division (the pool floors: an odd trailing row or column of conv
+ * pixels belongs to no window and is not computed, though the windows beside it read it as a tap), per
+ * image n, window (py, px) and output channel co:
+ *   acc_q = for each of the four conv pixels q = (2 py + dy, 2 px + dx), dy, dx in 0..1: the sum over ci
+ *         and the taps (ky, kx) in 0..2 with iy = 2 py + dy - 1 + ky in [0, H) and ix = 2 px + dx - 1 + kx
+ *         in [0, W) of x[n, iy, ix, ci] * w[co][ci][ky][kx]
+ *         (a tap outside the image contributes zero and never reads the neighbouring image; products
+ *         of bf16 operands, accumulated in f32 on the MFMA)
+ *   r_q = fmaf(acc_q, scale[co], shift[co])      (scale may be negative: the fold comes before the maximum)
+ *   m   = the maximum of the four r_q with torch's update `r > m || isnan(r)`: a NaN among them gives NaN
+ *   y   = m <= 0 ? +0 : m                        (a NaN stays NaN)
+ *   out = y, rounded once to bf16 (nearest-even) for a bf16 output
+ *   x              (n_images, H, W, cin) bf16, channels-last; H, W >= 2
+ *   cin            a multiple of 64 in [64, 2048];  cout a multiple of 64 in [64, 512]
+ *   weight_packed  mvn_conv3x3_pool_packed_weight_bytes(cin, cout) = 9 * (cin / 32) * (cout / 16) * 64 * 8 * 2
+ *                  bytes: bf16 as [tap = ky*3 + kx][kp 0..cin/32-1][m 0..cout/16-1][lane 0..63][j 0..7]
+ *                    = w[16 m + (lane & 15)][32 kp + 8 (lane >> 4) + j][ky][kx]
+ *                  (w the Conv2d weight (cout, cin, 3, 3), rounded to bf16)
+ *   scale, shift   (cout) f32: the convolution's bias and the BatchNorm folded
+ *   out            (n_images, Hp, Wp, cout) channels-last, out_dtype MVN_DTYPE_BF16 | MVN_DTYPE_F32; the two
+ *                  agree bit for bit after rounding the f32 one
+ * Order of the sum: the K-steps it = 0 .. 9 cin / 32 - 1 (tap-major: it = tap * cin / 32 + kp, each step the
+ * MFMA's 32 channels) go to four accumulators a_s, a_s taking the steps [s per, (s + 1) per) within the range,
+ * per = ceil(9 cin / 32 / 4) rounded up to even, each in ascending order; acc = ((a_0 + a_1) + a_2) + a_3 in
+ * f32.  One fixed order for every launch: deterministic, no atomics.
+ * x and out stay below 2^31 bytes and every pointer is 16-byte aligned.  A NaN or infinite input pixel
+ * (iy, ix) reaches exactly the windows (py, px) with 2 py - 1 <= iy <= 2 py + 2 and 2 px - 1 <= ix <= 2 px + 2
+ * of its own image, in all channels (an infinity against a zero weight is a NaN, as in torch; a -inf
+ * or any value the ReLU removes does not survive it).  No load touches a byte outside an operand
+ * (a range-checked buffer resource over x) and no store a byte outside out.
+ * Checked before any HIP call, all MVN_ERR_ARG: a null pointer, a channel count outside its set, an
+ * unknown out_dtype, n_images < 0, H < 2 or W < 2, a tensor of 2^31 bytes or more, a pointer
+ * off its alignment.  n_images == 0 returns MVN_OK without a launch.  The size function returns 0 for
+ * channels outside the sets.  Stream-ordered, allocates nothing, reentrant.
+ */
+size_t mvn_conv3x3_pool_packed_weight_bytes(int cin, int cout);
+int mvn_conv3x3_pool(const void* x, const void* weight_packed, const float* scale, const float* shift, void* out,
+                     int out_dtype, int64_t n_images, int H, int W, int cin, int cout, void* stream);
+
+/*
+ * The rest of a confidence head (pose_resnet.py:156-174): the mean over the pixels, Linear(c0, c1) +
+ * ReLU + Linear(c1, c2) + ReLU + Linear(c2, n) and the Sigmoid, in one launch, all in f32 on the vector
+ * ALU, one block per image.  Per image m:
+ *   s[c]    = +0, then s[c] = s[c] + pooled[m, p, c] for the pixels p = 0 .. hw - 1 ascending
+ *   x0[c]   = s[c] / float(hw)                                  (IEEE division)
+ *   x1[o]   = relu_keep_nan(chain(W1, b1, x0)[o]),  x2[o] = relu_keep_nan(chain(W2, b2, x1)[o]),
+ *   z[o]    = chain(W3, b3, x2)[o]
+ *     with chain(W, b, v)[o]: acc = b[o], then acc = fmaf(W[o][i], v[i], acc) for i ascending
+ *   out[m, o] = z[o]                           activation MVN_ACT_NONE (the logits)
+ *             = 1.0f / (1.0f + expf(-z[o]))    MVN_ACT_SIGMOID: expf of the HIP device library (OCML's
+ *               exp_f32, documented in the HIP math API reference with a maximum error of 1 ulp), one
+ *               f32 add and one IEEE f32 division beside it
+ *   pooled         (n_images, hw, c0) f32: the second mvn_conv3x3_pool's f32 output with its h x w pixels flat
+ *   c0, c1, c2     multiples of 64 in [64, 512];  1 <= n <= 32;  hw >= 1
+ *   params         mvn_confidence_tail_packed_bytes(c0, c1, c2, n) bytes of f32, each weight transposed
+ *                  (in, out) so that the threads of consecutive outputs load consecutive words:
+ *                    params[i * c1 + o]            = W1[o][i]      i < c0, o < c1
+ *                    params[O1 + o]                = b1[o]         O1 = c0 c1
+ *                    params[O2 + i * c2 + o]       = W2[o][i]      O2 = O1 + c1;  i < c1, o < c2
+ *                    params[O3 + o]                = b2[o]         O3 = O2 + c1 c2
+ *                    params[O4 + i * n + o]        = W3[o][i]      O4 = O3 + c2;  i < c2, o < n
+ *                    params[O5 + o]                = b3[o]         O5 = O4 + c2 n
+ *   out            (n_images, n) f32
+ * pooled stays below 2^31 bytes.  Deterministic; an image's NaN or infinity stays in its own row of out.
+ * Checked before any HIP call, all MVN_ERR_ARG: a null pointer, a width or n outside its set, an unknown
+ * activation, n_images < 0, hw < 1, pooled of 2^31 bytes or more, a pointer off its 4-byte alignment.
+ * n_images == 0 returns MVN_OK without a launch.  The size function returns 0 for widths outside the
+ * sets.  Stream-ordered, allocates nothing, reentrant.
+ */
+#define MVN_ACT_NONE     0
+#define MVN_ACT_SIGMOID  1
+size_t mvn_confidence_tail_packed_bytes(int c0, int c1, int c2, int n);
+int mvn_confidence_tail(const float* pooled, const float* params, float* out, int64_t n_images, int hw, int c0,
+                        int c1, int c2, int n, int activation, void* stream);
 
 /*
  * 2D soft-argmax of heatmaps.  Replaces mvn/utils/op.py:11-47 (integrate_tensor_2d) with

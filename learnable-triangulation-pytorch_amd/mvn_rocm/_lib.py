@@ -23,6 +23,7 @@ MVN_LAYOUT_NCDHW, MVN_LAYOUT_NDHWC = 0, 1
 MVN_LAYOUT_NCHW, MVN_LAYOUT_NHWC = 0, 1
 MVN_PRECISION_EXACT, MVN_PRECISION_FAST = 0, 1
 MVN_SKIP_NONE, MVN_SKIP_IDENTITY, MVN_SKIP_POINTWISE = 0, 1, 2
+MVN_ACT_NONE, MVN_ACT_SIGMOID = 0, 1
 
 _c_int, _c_void_p, _c_float, _c_i64, _c_size_t = (
     ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t)
@@ -100,6 +101,10 @@ SIGNATURES = {
     "mvn_conv3x3": (_c_int, [_c_void_p] * 5 + [_c_i64] + [_c_int] * 4 + [_c_void_p]),
     "mvn_stem_packed_weight_bytes": (_c_size_t, []),
     "mvn_stem": (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 4 + [_c_i64, _c_int, _c_int, _c_void_p]),
+    "mvn_conv3x3_pool_packed_weight_bytes": (_c_size_t, [_c_int, _c_int]),
+    "mvn_conv3x3_pool": (_c_int, [_c_void_p] * 5 + [_c_int, _c_i64] + [_c_int] * 4 + [_c_void_p]),
+    "mvn_confidence_tail_packed_bytes": (_c_size_t, [_c_int] * 4),
+    "mvn_confidence_tail": (_c_int, [_c_void_p] * 3 + [_c_i64] + [_c_int] * 6 + [_c_void_p]),
     "mvn_unproject_backward": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
                                         _c_void_p, _c_void_p] + [_c_int] * 8 + [_c_int, _c_int, _c_void_p]),
     "mvn_unproject_backward_workspace_bytes": (_c_size_t, [_c_int] * 5),

@@ -565,6 +565,54 @@ def _(images, packed, scale, shift):
     return images.new_empty(_stem_out_shape(images), dtype=torch.bfloat16)
 
 
+# --------------------------------------------------------------------------- confidence heads
+def _pool_out_shape(x: Tensor, scale: Tensor):
+    M, H, W, _ = x.shape
+    return (M, H // 2, W // 2, scale.shape[0])
+
+
+@_op("conv3x3_pool")
+def conv3x3_pool(x: Tensor, packed: Tensor, scale: Tensor, shift: Tensor, out_dtype: int) -> Tensor:
+    """x (M,H,W,Cin) bf16 channels-last -> relu(maxpool2(bn(conv3x3(x, padding 1)))) as (M,H/2,W/2,Cout) of dtype
+    code `out_dtype`, Cout = len(scale) (csrc/confidence_head.hip)."""
+    _require_gpu(x, packed, scale, shift)
+    M, H, W, cin = x.shape
+    out = torch.empty(_pool_out_shape(x, scale), dtype=_CODE_DTYPE[out_dtype], device=x.device)
+    if M == 0:                            # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_conv3x3_pool(x.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                        out.data_ptr(), out_dtype, M, H, W, cin, scale.shape[0], _stream(x))
+    _lib.check(code, "mvn_conv3x3_pool")
+    return out
+
+
+@conv3x3_pool.register_fake
+def _(x, packed, scale, shift, out_dtype):
+    return x.new_empty(_pool_out_shape(x, scale), dtype=_CODE_DTYPE[out_dtype])
+
+
+@_op("confidence_tail")
+def confidence_tail(pooled: Tensor, packed: Tensor, c1: int, c2: int, n: int, sigmoid: bool) -> Tensor:
+    """pooled (M,h,w,C0) f32 channels-last, packed f32 (pack_confidence_tail) -> the sigmoid (or the logits) of
+    Linear(C0,c1) relu Linear(c1,c2) relu Linear(c2,n) of the mean over the pixels, (M,n) f32
+    (csrc/confidence_head.hip)."""
+    _require_gpu(pooled, packed)
+    M, h, w, c0 = pooled.shape
+    out = torch.empty((M, n), dtype=torch.float32, device=pooled.device)
+    if M == 0:                            # empty batch: nothing to launch
+        return out
+    code = _lib.load().mvn_confidence_tail(pooled.data_ptr(), packed.data_ptr(), out.data_ptr(), M, h * w, c0, int(c1),
+                                           int(c2), int(n), _lib.MVN_ACT_SIGMOID if sigmoid else _lib.MVN_ACT_NONE,
+                                           _stream(pooled))
+    _lib.check(code, "mvn_confidence_tail")
+    return out
+
+
+@confidence_tail.register_fake
+def _(pooled, packed, c1, c2, n, sigmoid):
+    return pooled.new_empty((pooled.shape[0], n), dtype=torch.float32)
+
+
 # --------------------------------------------------------------------------- 2D soft-argmax
 @_op("softargmax2d")
 def softargmax2d(hm: Tensor, softmax: bool, multiplier: float, return_maps: bool,

@@ -7,9 +7,10 @@ in the same launch: the 256-channel maps are not written.
 
 ``DeconvHeadEval`` is the head alone, from ``layer4``'s output to ``(heatmaps, features)``;
 ``BackboneEval`` is the reference's ``PoseResNet.forward`` with its own trunk modules in front of
-it.  The confidence heads stay with torch, and by default so does the ResNet trunk;
+it.  By default the confidence heads and the ResNet trunk stay with torch;
 ``BackboneEval.from_reference(..., trunk="kernels")`` runs ``layer1`` .. ``layer4`` on ``resnet.TrunkEval``
-(DESIGN.md §4.18).  Eval mode, inference-only.
+ and ``confidences="kernels"`` the heads on ``confidence.ConfidenceHeadEval`` (§4.20).
+Eval mode, inference-only.
 """
 from __future__ import annotations
 
@@ -330,7 +331,8 @@ _TRUNK = ("conv1", "bn1", "relu", "maxpool", "layer1", "layer2", "layer3", "laye
 class BackboneEval(nn.Module):
     """The reference's ``PoseResNet.forward`` (pose_resnet.py:293-318), eval mode: its own trunk modules
     ``conv1`` ... ``layer4`` and optional ``alg_confidences`` / ``vol_confidences`` heads, kept as they are
-    and called in the reference's order, then ``DeconvHeadEval``.  Returns the reference's 4-tuple
+    (or replaced on request: ``from_reference``) and called in the reference's order, then
+    ``DeconvHeadEval``.  Returns the reference's 4-tuple
     ``(heatmaps, features, alg_confidences, vol_confidences)``, None where the backbone has no such
     head (or ``heatmaps=False``); with ``process_features`` (``DeconvHeadEval``) the features are the
     model's 32-channel ones.  The module adds no arithmetic of its own.  The trunk modules are
@@ -347,16 +349,22 @@ class BackboneEval(nn.Module):
 
     @classmethod
     def from_reference(cls, backbone, device="cuda", feature_dtype=torch.bfloat16, heatmaps=True,
-                       process_features=None, trunk="torch", stem="torch"):
+                       process_features=None, trunk="torch", stem="torch", confidences="torch"):
         """``trunk="torch"`` (the default) keeps the backbone's own ``conv1`` ... ``layer4``; ``trunk="kernels"``
         runs ``layer1`` .. ``layer4`` through ``resnet.TrunkEval``, whose bfloat16
-        channels-last output the head reads without a copy and the confidence heads, which stay torch
+        channels-last output the head reads without a copy and the confidence heads, while they stay torch
         modules, get cast to their parameters' dtype.  ``stem`` is passed on to ``TrunkEval``: ``"kernels"``
-        runs ``conv1, bn1, relu, maxpool`` as one launch too and needs ``trunk="kernels"``."""
+        runs ``conv1, bn1, relu, maxpool`` as one launch too and needs ``trunk="kernels"``.
+        ``confidences="torch"`` (the default) keeps the backbone's own ``alg_confidences`` and
+        ``vol_confidences`` objects; ``"kernels"`` replaces each head the backbone has with a
+        ``confidence.ConfidenceHeadEval``, which reads the kernel trunk's output as it is
+        (no float32 cast is made then) and takes one cast-and-permute pass behind the torch trunk."""
         if trunk not in ("torch", "kernels"):
             raise ValueError(f"BackboneEval: trunk must be 'torch' or 'kernels', got {trunk!r}")
         if stem not in ("torch", "kernels"):
             raise ValueError(f"BackboneEval: stem must be 'torch' or 'kernels', got {stem!r}")
+        if confidences not in ("torch", "kernels"):
+            raise ValueError(f"BackboneEval: confidences must be 'torch' or 'kernels', got {confidences!r}")
         if stem == "kernels" and trunk != "kernels":
             raise ValueError("BackboneEval: stem='kernels' needs trunk='kernels': the kernel stem writes channels-last "
                              f"bfloat16 for TrunkEval, got trunk={trunk!r}")
@@ -370,8 +378,15 @@ class BackboneEval(nn.Module):
         else:
             trunk_module = nn.Sequential(*(getattr(backbone, n) for n in _TRUNK))
         head = DeconvHeadEval.from_reference(backbone, device, feature_dtype, heatmaps, process_features)
-        return cls(trunk_module, head, getattr(backbone, "alg_confidences", None),
-                   getattr(backbone, "vol_confidences", None), cast_for_confidences=trunk == "kernels")
+        alg, vol = getattr(backbone, "alg_confidences", None), getattr(backbone, "vol_confidences", None)
+        if confidences == "kernels":
+            from .confidence import ConfidenceHeadEval
+            try:
+                alg, vol = (None if h is None else ConfidenceHeadEval.from_reference(h, device=device) for h in (alg, vol))
+            except RuntimeError as e:
+                raise RuntimeError(f"BackboneEval: {e}") from None
+        return cls(trunk_module, head, alg, vol,
+                   cast_for_confidences=trunk == "kernels" and confidences == "torch")
 
     def forward(self, x):
         _inference_only("BackboneEval", x, instead="the backbone itself, which autograd records")

@@ -4,6 +4,8 @@ kernels: ``process_features``, a ``Conv2d(256, 32, 1)``, as ``feature_conv``
 feature maps to the joints: ``feature_conv``, ``v2v.unproject_channels_last`` and ``v2v.V2VEval``,
 composed and nothing else.  ``VolumetricModelEval`` puts ``backbone.BackboneEval`` in front of it:
 images to joints, with ``process_features`` optionally inside the head's last launch.
+``AlgebraicModelEval`` is the algebraic model (triangulation.py:149-200) in one call: ``BackboneEval`` and
+``multiview.triangulate_from_heatmaps``.
 """
 from __future__ import annotations
 
@@ -175,17 +177,18 @@ class VolumetricModelEval(nn.Module):
 
     @classmethod
     def from_reference(cls, model, device="cuda", feature_dtype=torch.bfloat16, half_res="kernels", deep="kernels",
-                       precision=None, fused=FUSED_DEFAULT, trunk="torch", stem="torch"):
+                       precision=None, fused=FUSED_DEFAULT, trunk="torch", stem="torch", confidences="torch"):
         """``model.backbone`` through ``BackboneEval.from_reference`` (``heatmaps=False``; with ``fused`` it
         is given ``model.process_features``; ``trunk`` is passed on: ``"kernels"`` runs the ResNet stages on
-        ``resnet.TrunkEval``, DESIGN.md §4.18, and with it ``stem="kernels"`` the stem in one launch, §4.19)
+        ``resnet.TrunkEval``, DESIGN.md §4.18, and with it ``stem="kernels"`` the stem in one launch, §4.19;
+        ``confidences="kernels"`` runs the confidence heads on ``confidence.ConfidenceHeadEval``, §4.20)
         and the rest of ``model`` through ``VolumetricEval.from_reference``.  ``fused`` defaults to what was measured faster (DESIGN.md
         §4.17)."""
         from .backbone import BackboneEval
         vol = VolumetricEval.from_reference(model, device, feature_dtype, half_res, deep, precision)
         bb = BackboneEval.from_reference(model.backbone, device, feature_dtype, heatmaps=False,
                                          process_features=model.process_features if fused else None, trunk=trunk,
-                                         stem=stem)
+                                         stem=stem, confidences=confidences)
         return cls(bb, vol, fused)
 
     def forward(self, images, proj_matricies, coord_volumes):
@@ -199,3 +202,52 @@ class VolumetricModelEval(nn.Module):
             vol_confidences = vol_confidences.view(B, N, *vol_confidences.shape[1:])
         run = self.volumetric.from_projected if self.fused else self.volumetric
         return run(features, proj_matricies, coord_volumes, vol_confidences)
+
+
+class AlgebraicModelEval(nn.Module):
+    """``AlgebraicTriangulationNet.forward`` (triangulation.py:149-200) from the images to the joints, eval
+    mode: ``backbone.BackboneEval`` (``heatmaps=True``) over ``model.backbone`` on the images as
+    (B * N, 3, H, W), then ``multiview.triangulate_from_heatmaps`` on its heatmaps with the model's
+    ``heatmap_multiplier`` and ``heatmap_softmax``, the images' (H, W) as ``image_shape`` and, with
+    ``use_confidences``, the backbone's ``alg_confidences`` (without: None, the reference's all ones).
+
+    ``module(images (B, N, 3, H, W), proj_matricies (B, N, 3, 4))`` returns the reference's 4-tuple:
+    keypoints_3d (B, J, 3), keypoints_2d (B, N, J, 2) in image pixels, the normalised heatmaps
+    (B, N, J, h, w) and the normalised confidences (B, N, J).  The module adds no arithmetic of its own.
+    Inference-only."""
+
+    def __init__(self, backbone, use_confidences, heatmap_softmax, heatmap_multiplier):
+        super().__init__()
+        if use_confidences and getattr(backbone, "alg_confidences", None) is None:
+            raise RuntimeError("AlgebraicModelEval: use_confidences needs a backbone with an alg_confidences head, "
+                               "got alg_confidences=None")
+        self.backbone = backbone
+        self.use_confidences = bool(use_confidences)
+        self.heatmap_softmax = bool(heatmap_softmax)
+        self.heatmap_multiplier = float(heatmap_multiplier)
+
+    @classmethod
+    def from_reference(cls, model, device="cuda", feature_dtype=torch.bfloat16, trunk="torch", stem="torch",
+                       confidences="torch"):
+        """``model.backbone`` through ``BackboneEval.from_reference`` with ``trunk``, ``stem`` and
+        ``confidences`` passed on, and the model's ``use_confidences``,
+        ``heatmap_softmax`` and ``heatmap_multiplier``.  ``use_confidences`` with a backbone that has no
+        ``alg_confidences`` raises."""
+        from .backbone import BackboneEval
+        if model.use_confidences and getattr(model.backbone, "alg_confidences", None) is None:
+            raise RuntimeError("AlgebraicModelEval: use_confidences needs a backbone with an alg_confidences head, "
+                               f"{type(model.backbone).__name__} has none")
+        bb = BackboneEval.from_reference(model.backbone, device, feature_dtype, heatmaps=True, trunk=trunk, stem=stem,
+                                         confidences=confidences)
+        return cls(bb, model.use_confidences, model.heatmap_softmax, model.heatmap_multiplier)
+
+    def forward(self, images, proj_matricies):
+        from .multiview import triangulate_from_heatmaps
+        _inference_only("AlgebraicModelEval", images, instead="the model itself, which autograd records")
+        if images.dim() != 5:
+            raise RuntimeError(f"AlgebraicModelEval: images must be (B, N, 3, H, W), got {tuple(images.shape)}")
+        B, N = images.shape[:2]
+        heatmaps, _, alg_confidences, _ = self.backbone(images.reshape(B * N, *images.shape[2:]))
+        return triangulate_from_heatmaps(heatmaps, proj_matricies, alg_confidences if self.use_confidences else None,
+                                         image_shape=tuple(images.shape[3:]), heatmap_multiplier=self.heatmap_multiplier,
+                                         heatmap_softmax=self.heatmap_softmax)
